@@ -83,6 +83,33 @@ def flops_per_reliable(Vcb: int) -> float:
     return float(Vcb) * (mdagm + 96 + 48 + 48)
 
 
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, x, stats, seed, rank, world):
+    """Write what the last timed solve handed back: the solution spinor as
+    float64 [sites, 4, 3, 2] (re, im) and the solve statistics
+    [iters, reliable_updates, resid]. A solution larger than DUMP_MAX_BYTES
+    is reduced to a fixed, seeded sample of checkerboard sites (ascending
+    site index), the same sites for the same --seed and lattice."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    sol = torch.view_as_real(x.to_complex()[0])            # [Vcb, 4, 3, 2]
+    n_sites = sol.shape[0]
+    keep = DUMP_MAX_BYTES // (sol[0].numel() * 8)
+    if n_sites > keep:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(seed + 200)
+        sites = torch.randperm(n_sites, generator=gen)[:keep].sort().values
+        sol = sol[sites.to(sol.device)]
+    np.save(os.path.join(out_dir, f"solution{suffix}.npy"),
+            sol.to("cpu", torch.float64).contiguous().numpy())
+    np.save(os.path.join(out_dir, f"solve_stats{suffix}.npy"),
+            np.array([stats.iters, stats.reliable_updates, stats.resid],
+                     dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,10 +131,22 @@ def main():
     ap.add_argument("--seed", type=int, default=777)
     ap.add_argument("--device", default=None,
                     help="override (cpu for harness tests; default cuda:LOCAL_RANK)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution of the "
+                         "last timed solve (and its iteration statistics) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; the headline "
+                         "solve is all this benchmark measures, so there is "
+                         "nothing extra to run yet")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     dims = tuple(int(d) for d in args.lattice.split(","))
-    rank, world = comms.init_comms()
+    # a CPU run talks over gloo even where a GPU is visible: the default
+    # backend choice would bind rank r to cuda:r, which need not exist
+    on_cpu = args.device is not None and args.device.startswith("cpu")
+    rank, world = comms.init_comms(backend="gloo" if on_cpu else None)
     assert world == args.gpus or "WORLD_SIZE" not in os.environ, \
         f"world {world} != --gpus {args.gpus}"
     if args.device:
@@ -136,6 +175,7 @@ def main():
             counts["iters"] += st.iters
             counts["reliable"] += st.reliable_updates
             counts["resid"] = st.resid
+            counts["last"] = st
         return st
 
     for _ in range(args.warmup):
@@ -159,6 +199,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, counts["last"], args.seed, rank, world)
 
     ms_per_step = elapsed / args.steps * 1000.0
     total_flops = (flops_per_iter(geo.volume_cb) * counts["iters"]

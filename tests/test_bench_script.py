@@ -23,7 +23,13 @@ def _launch_two_rank(port):
              "--steps", "1", "--warmup", "0", "--maxiter", "4",
              "--lattice", "4,4,4,8", "--sloppy", "double", "--device", "cpu"],
             env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = [p.communicate(timeout=300) for p in procs]
+    try:
+        outs = [p.communicate(timeout=300) for p in procs]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     return procs, outs
 
 
@@ -56,3 +62,36 @@ def test_bench_single_rank_cpu():
     assert out.returncode == 0, out.stderr
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed solve's solution and statistics;
+    the same arguments give the same inputs, so two runs agree (the CPU
+    oracle path is deterministic, so they agree bit for bit). --full is
+    accepted and leaves the result line's fields in place."""
+    import numpy as np
+
+    def run(out_dir, *extra):
+        out = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2",
+             "--warmup", "0", "--maxiter", "4", "--lattice", "4,4,4,8",
+             "--sloppy", "double", "--device", "cpu",
+             "--dump-outputs", str(out_dir), *extra],
+            capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr
+        return json.loads(
+            [l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    rec = run(tmp_path / "a")
+    rec_full = run(tmp_path / "b", "--full")
+    for r in (rec, rec_full):
+        assert r["steps"] == 2 and r["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in r
+    sol = np.load(tmp_path / "a" / "solution.npy")
+    assert sol.dtype == np.float64 and sol.shape == (4 * 4 * 4 * 8 // 2, 4, 3, 2)
+    assert np.isfinite(sol).all() and np.abs(sol).max() > 0
+    stats = np.load(tmp_path / "a" / "solve_stats.npy")
+    assert stats.dtype == np.float64 and stats[0] == rec["config"]["iters_per_solve"]
+    assert np.array_equal(sol, np.load(tmp_path / "b" / "solution.npy"))
+    assert np.array_equal(stats, np.load(tmp_path / "b" / "solve_stats.npy"))
