@@ -108,7 +108,8 @@ def main():
     ap.add_argument("--lattice", default="32,32,32,64")
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--families", default="wilson",
-                    help="comma list: wilson,staggered,mobius,dwf5,all,sweep")
+                    help="comma list: wilson,staggered,mobius,mobius_pc,dwf5,"
+                         "all,sweep")
     args = ap.parse_args()
     fams = set(args.families.split(","))
     if "all" in fams:
@@ -142,6 +143,8 @@ def main():
         results.update(bench_staggered(geo, u, args.reps))
     if "mobius" in fams:
         results.update(bench_mobius(geo, u, max(args.reps // 5, 3)))
+    if "mobius_pc" in fams:
+        results.update(bench_mobius_pc(geo, u, max(args.reps // 5, 3)))
     if "dwf5" in fams:
         results.update(bench_dwf5(geo, max(args.reps, 20)))
     if "mrhs" in fams:
@@ -266,6 +269,46 @@ def bench_mobius(geo, u, reps, Ls=12):
     return out
 
 
+def bench_mobius_pc(geo, u, reps, Ls=12, rounds=5):
+    """DiracMobiusPC.MdagM, unfused vs the fused domain-wall kernel
+    (fused=True), same process, alternating timed windows; median over
+    `rounds`. Flop model: 4 hop+s-stage passes over Vcb*Ls sites."""
+    from quda_amd.models.dwf import DiracMobiusPC
+    dev = "cuda"
+    out = {}
+    for prec, recon in [("double", "none"), ("single", "none"),
+                        ("half", "twelve")]:
+        g = GaugeField(geo, prec, dev, reconstruct=recon).from_complex(u)
+        ops = {"unfused": DiracMobiusPC(g, 0.04, 1.8, Ls, fused=False),
+               "fused": DiracMobiusPC(g, 0.04, 1.8, Ls, fused=True)}
+        psi = SpinorField(geo, prec, dev, n_parity=1, ls=Ls).gaussian_(seed=9)
+        res = SpinorField(geo, prec, dev, n_parity=1, ls=Ls)
+        tmp = SpinorField(geo, prec, dev, n_parity=1, ls=Ls)
+        for d in ops.values():
+            for _ in range(3):
+                d.MdagM(res, psi, tmp)
+        torch.cuda.synchronize()
+        times = {k: [] for k in ops}
+        for _ in range(rounds):
+            for k, d in ops.items():
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    d.MdagM(res, psi, tmp)
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) / reps)
+        flops = 4 * geo.volume_cb * Ls * ops["fused"].flops_per_site()
+        rc = 18 if recon == "none" else 12
+        for k, ts in times.items():
+            ts.sort()
+            dt = ts[len(ts) // 2]
+            key = f"mobius_pc_MdagM_Ls{Ls}/{prec}/r{rc}/{k}"
+            out[key] = flops / dt / 1e9
+            print(f"{key:44s} {dt*1e3:8.3f} ms  {out[key]:8.0f} GFLOPS  "
+                  f"(min {ts[0]*1e3:.3f} max {ts[-1]*1e3:.3f} ms)",
+                  flush=True)
+        del ops, psi, res, tmp, g
+        torch.cuda.empty_cache()
+    return out
 
 
 def bench_mrhs(geo, u, reps):

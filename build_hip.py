@@ -31,6 +31,7 @@ KERNEL_SOURCES = [
     "dslash_wilson_q.hip",
     "dslash_staggered.hip",
     "dslash_dwf.hip",
+    "dslash_dwf_fused.hip",
     "dslash_wilson_mrhs.hip",
     "coarse.hip",
     "heatbath.hip",

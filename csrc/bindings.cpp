@@ -354,6 +354,95 @@ static void dwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
   check_launch("dwf5");
 }
 
+// Fused domain-wall kernel (csrc/dslash_dwf_fused.h). Every argument is
+// validated here: a bad call raises and nothing is launched.
+static void dwf_fused(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                      at::Tensor in_n, at::Tensor gauge, at::Tensor x,
+                      at::Tensor x_n, c10::optional<at::Tensor> W,
+                      std::vector<int64_t> dims, int64_t parity_offset,
+                      int64_t Vcb, int64_t Ls, int64_t parity, bool dagger,
+                      bool xpay, double a, int64_t recon) {
+  TORCH_CHECK(Ls >= 1 && Ls <= QA_DWF_FUSED_LS_MAX, "dwf_fused: Ls = ", Ls,
+              " outside 1..", QA_DWF_FUSED_LS_MAX);
+  TORCH_CHECK(dims.size() == 4 && Vcb > 0, "dwf_fused: bad lattice");
+  TORCH_CHECK(dims[0] > 0 && dims[0] % 2 == 0 && dims[1] > 0 && dims[2] > 0 &&
+                  dims[3] > 0 &&
+                  dims[0] * dims[1] * dims[2] * dims[3] == 2 * Vcb,
+              "dwf_fused: dims do not match Vcb");
+  TORCH_CHECK(parity == 0 || parity == 1, "dwf_fused: parity must be 0 or 1");
+  TORCH_CHECK(out.is_cuda(), "dwf_fused: fields must live on the GPU");
+  const int prec = prec_of(out);
+  TORCH_CHECK(prec <= 2, "dwf_fused: double, single or half only");
+  TORCH_CHECK(recon == 18 || (recon == 12 && prec != 0),
+              "dwf_fused: reconstruct ", recon, " unsupported at this precision");
+  const int64_t stride = Ls * Vcb;
+  auto check_field = [&](const at::Tensor &t, const at::Tensor &n,
+                         const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == out.device(), "dwf_fused: ", name,
+                " on a different device");
+    TORCH_CHECK(t.scalar_type() == out.scalar_type(), "dwf_fused: ", name,
+                " dtype differs from out");
+    TORCH_CHECK(t.is_contiguous(), "dwf_fused: ", name, " not contiguous");
+    TORCH_CHECK(t.dim() == 4 && t.size(0) == 1 && t.size(2) == stride &&
+                    t.size(3) == chunk_w_of(t) &&
+                    t.size(1) * t.size(3) == 24,
+                "dwf_fused: ", name, " is not a single-parity field with "
+                "chunk stride Ls*Vcb");
+    if (prec == 2) {
+      TORCH_CHECK(n.is_cuda() && n.device() == out.device() &&
+                      n.scalar_type() == at::kFloat && n.is_contiguous() &&
+                      n.numel() == stride,
+                  "dwf_fused: ", name, " norm is not float32 [Ls*Vcb]");
+    }
+  };
+  check_field(out, out_n, "out");
+  check_field(in, in_n, "in");
+  if (xpay) check_field(x, x_n, "x");
+  TORCH_CHECK(gauge.is_cuda() && gauge.device() == out.device() &&
+                  gauge.scalar_type() == out.scalar_type() &&
+                  gauge.is_contiguous() &&
+                  gauge.numel() == 2 * 8 * recon * Vcb,
+              "dwf_fused: gauge is not a stencil-layout field of this "
+              "precision/reconstruct");
+  {
+    // the stencil reads neighbors of `in` while other workgroups store
+    // `out`: their memory must not overlap (out may alias x)
+    const char *o0 = (const char *)out.data_ptr(), *o1 = o0 + out.nbytes();
+    const char *i0 = (const char *)in.data_ptr(), *i1 = i0 + in.nbytes();
+    TORCH_CHECK(o1 <= i0 || i1 <= o0, "dwf_fused: out aliases in");
+  }
+  const double *Wp = nullptr;
+  at::Tensor Wc;
+  if (W) {
+    TORCH_CHECK(W->device().is_cpu() && W->scalar_type() == at::kDouble,
+                "dwf_fused: W must be a float64 host tensor");
+    TORCH_CHECK(W->dim() == 3 && W->size(0) == 2 && W->size(1) == Ls &&
+                    W->size(2) == Ls,
+                "dwf_fused: W must have shape [2, Ls, Ls]");
+    Wc = W->contiguous();
+    Wp = Wc.data_ptr<double>();
+  }
+  DwfFusedCall c{};
+  c.out = field_of(out, out_n, stride);
+  c.in = field_of(in, in_n, stride);
+  c.x = xpay ? field_of(x, x_n, stride) : c.out;
+  c.gauge = gauge.data_ptr();
+  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
+  c.parity_offset = (int)parity_offset;
+  c.Vcb = Vcb;
+  c.Ls = (int)Ls;
+  c.parity = (int)parity;
+  c.dagger = dagger;
+  c.xpay = xpay;
+  c.a = a;
+  c.recon = (int)recon;
+  c.prec = prec;
+  c.W = Wp;
+  TORCH_CHECK(launch_dwf_fused(c, stream()),
+              "dwf_fused: no kernel for this configuration");
+  check_launch("dwf_fused");
+}
+
 static void zdwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
                   at::Tensor in_n, at::Tensor x, at::Tensor x_n,
                   int64_t Vcb4, int64_t Ls, bool xpay, double a_re,
@@ -442,6 +531,10 @@ static void set_dslash_waves(int64_t w) {
 }
 
 static void set_dslash_lds(int64_t v) { qa_dslash_lds_ref() = (int)v; }
+
+static void set_dwf_fused_ns(int64_t v) {
+  if (v == 16 || v == 32) qa_dwf_fused_ns_ref() = (int)v;
+}
 
 // ---------------------------------------------------------------------------
 // HIP-IPC remote-write halos (role of comm_target.cpp:41-134 P2P
@@ -648,6 +741,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_face_ptr", &pack_face_ptr,
         "pack a halo face into a raw (IPC peer) pointer");
   m.def("dwf5", &dwf5, "DWF/Moebius 5th-dim ops (Ds apply / M5 inverse)");
+  m.def("dwf_fused", &dwf_fused,
+        "fused domain-wall kernel: out = [x +] a * W_chi (Dhat in), all Ls "
+        "slices in one launch",
+        py::arg("out"), py::arg("out_n"), py::arg("in"), py::arg("in_n"),
+        py::arg("gauge"), py::arg("x"), py::arg("x_n"), py::arg("W"),
+        py::arg("dims"), py::arg("parity_offset"), py::arg("Vcb"),
+        py::arg("Ls"), py::arg("parity"), py::arg("dagger"), py::arg("xpay"),
+        py::arg("a"), py::arg("recon"));
+  m.def("set_dwf_fused_ns", &set_dwf_fused_ns,
+        "fused domain-wall kernel: sites per workgroup for single/half "
+        "(16 or 32)");
+  m.attr("DWF_FUSED_LS_MAX") = (int)QA_DWF_FUSED_LS_MAX;
   m.def("zdwf5", &zdwf5, "zMobius per-slice-complex 5th-dim ops");
   m.def("eofa5", &eofa5, "EOFA rank-1 extended M5 ops");
   m.def("blas_op", &blas_op, "fused blas/reduction",

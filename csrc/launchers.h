@@ -214,6 +214,39 @@ struct Dwf5Call {
 void launch_dwf5(const Dwf5Call &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// fused domain-wall kernel (csrc/dslash_dwf_fused.h): for all Ls slices,
+//   out = [x +] a * W_chi (Dhat in),  W_chi = dense real Ls x Ls per chirality
+#define QA_DWF_FUSED_LS_MAX 16
+struct DwfFusedCall {
+  BlasField out, in, x;  // 5-d single-parity fields (Vcb = chunk stride Ls*Vcb4)
+  const void *gauge;     // stencil layout, like DslashCall
+  int Xdim[4];
+  int parity_offset;
+  long Vcb;              // 4-d cb volume
+  int Ls;                // 1..QA_DWF_FUSED_LS_MAX
+  int parity;
+  bool dagger;
+  bool xpay;
+  double a;
+  int recon;             // 18, or 12 for single/half
+  int prec;              // 0 double, 1 single, 2 half
+  const double *W;       // HOST [2][Ls][Ls] (upper, lower); null = identity
+};
+// sites per workgroup for single/half: 16 or 32 (set_dwf_fused_ns binding;
+// env QUDA_AMD_DWF_FUSED_NS seeds the default, see profiles/r03_dwf_fused.md)
+inline int &qa_dwf_fused_ns_ref() {
+  static int ns = [] {
+    const char *e = getenv("QUDA_AMD_DWF_FUSED_NS");
+    int v = e ? atoi(e) : 16;
+    return (v == 16 || v == 32) ? v : 16;
+  }();
+  return ns;
+}
+inline int qa_dwf_fused_ns() { return qa_dwf_fused_ns_ref(); }
+// false when (prec, recon, Ls) has no instantiation or W staging failed
+bool launch_dwf_fused(const DwfFusedCall &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // coarse-grid dslash on MFMA (csrc/coarse.hip)
 struct CoarseMfmaCall {
   const void *mats;  // [9][Na][Nc][Nc] complex64

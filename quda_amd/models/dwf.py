@@ -26,11 +26,26 @@ from ..ops import blas
 from ..ops.dispatch import dslash_wilson_slice, dwf5_op
 
 
+def _fused_default() -> bool:
+    import os
+    return os.environ.get("QUDA_AMD_DWF_FUSED", "0") not in ("", "0")
+
+
 class DiracMobius:
-    """Full 5-d Moebius operator."""
+    """Full 5-d Moebius operator.
+
+    fused=True routes the 4-d hops through the fused domain-wall kernel
+    (dispatch.dwf_fused_op): every s-stage between a Dhat and the next B is
+    folded into a dense per-chirality Ls x Ls matrix applied inside the hop
+    launch. None reads QUDA_AMD_DWF_FUSED (unset/0 = off)."""
+
+    # the dense-matrix folding below assumes the real Moebius s-structure;
+    # zMobius (complex) and EOFA (rank-1 extended A) keep the unfused path
+    _fused_capable = True
 
     def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int,
-                 b5: float = 1.5, c5: float = 0.5):
+                 b5: float = 1.5, c5: float = 0.5,
+                 fused: Optional[bool] = None):
         self.gauge = gauge
         self.geo = gauge.geo
         self.mf = float(mf)
@@ -41,6 +56,48 @@ class DiracMobius:
         d4 = 4.0 - self.m5
         self.alpha = 1.0 + self.b5 * d4
         self.beta = self.c5 * d4 - 1.0
+        self.fused = _fused_default() if fused is None else bool(fused)
+        self.s_mats = self._build_s_matrices()
+
+    def _build_s_matrices(self):
+        """float64 [2, Ls, Ls] (upper, lower chirality) dense forms of the
+        s-operators and the products the fused path needs. The blocks are
+        real, so the dagger is the transpose."""
+        import numpy as np
+        import torch
+        from ..ops import reference as ref
+
+        def pair(al, be):
+            return np.stack([ref._m5_matrix(self.Ls, al, be, self.mf, up,
+                                            False) for up in (True, False)])
+
+        A = pair(self.alpha, self.beta)
+        B = pair(self.b5, self.c5)
+        Ainv = np.linalg.inv(A)
+        T = lambda m: np.ascontiguousarray(np.swapaxes(m, 1, 2))
+        mats = {
+            "A": A, "B": B, "Ainv": Ainv, "BAinv": B @ Ainv,
+            "Adag": T(A), "Bdag": T(B), "Ainvdag": T(Ainv),
+            "AinvdagBdag": T(Ainv) @ T(B),
+        }
+        return {k: torch.from_numpy(np.ascontiguousarray(v))
+                for k, v in mats.items()}
+
+    def _use_fused(self, f: SpinorField) -> bool:
+        """Fused path: the native kernel where it applies, the composed
+        oracle on CPU; an unsupported GPU configuration (Ls > 16,
+        partitioned dims, quarter, reconstruct-8) keeps the unfused native
+        kernels."""
+        if not (self._fused_capable and getattr(self, "fused", False)):
+            return False
+        from ..ops.dispatch import dwf_fused_supported, on_gpu
+        if on_gpu(f):
+            return dwf_fused_supported(f, self.gauge)
+        return True
+
+    @property
+    def _b_is_identity(self) -> bool:
+        return self.c5 == 0.0 and self.b5 == 1.0
 
     # -- field helpers ------------------------------------------------------
     def new_spinor(self, precision=None, n_parity=1) -> SpinorField:
@@ -86,6 +143,8 @@ class DiracMobius:
     def M(self, out: SpinorField, inp: SpinorField, dagger: bool = False):
         """out_p = A in_p - (1/2) Dhat_p,1-p (B in_{1-p})  (both parities)."""
         assert inp.n_parity == 2
+        if self._use_fused(inp):
+            return self._M_fused(out, inp, dagger)
         t = self._tmp("mob_t", inp.parity_view(0))
         for p in (0, 1):
             op = out.parity_view(p)
@@ -105,6 +164,27 @@ class DiracMobius:
                 blas.axpy(-0.5, u, op)
         return out
 
+    def _M_fused(self, out, inp, dagger):
+        """M with the hop and the B^dag stage in one launch per parity."""
+        from ..ops.dispatch import dwf_fused_op
+        for p in (0, 1):
+            op = out.parity_view(p)
+            ip = inp.parity_view(p)
+            io = inp.parity_view(1 - p)
+            if not dagger:
+                src = io
+                if not self._b_is_identity:
+                    src = self._tmp("mob_t", ip)
+                    self.apply_B(src, io)
+                self.apply_A(op, ip)
+                dwf_fused_op(op, src, self.gauge, p, a=-0.5, x=op)
+            else:
+                self.apply_A(op, ip, dagger=True)
+                W = None if self._b_is_identity else self.s_mats["Bdag"]
+                dwf_fused_op(op, io, self.gauge, p, dagger=True, W=W,
+                             a=-0.5, x=op)
+        return out
+
     def MdagM(self, out, inp, tmp):
         self.M(tmp, inp, dagger=False)
         self.M(out, tmp, dagger=True)
@@ -122,6 +202,8 @@ class DiracMobiusPC(DiracMobius):
 
     def M(self, out: SpinorField, inp: SpinorField, dagger: bool = False):
         assert inp.n_parity == 1
+        if self._use_fused(inp):
+            return self._M_fused(out, inp, dagger)
         t = self._tmp("pc_t", inp)
         u = self._tmp("pc_u", inp)
         if not dagger:
@@ -146,6 +228,31 @@ class DiracMobiusPC(DiracMobius):
             self.apply_B(v, t, dagger=True)
             blas.copy(out, inp)
             blas.axpy(-0.25, v, out)
+        return out
+
+    def _M_fused(self, out, inp, dagger):
+        """Three launches: one 5th-dim op + two fused hops, each carrying
+        the dense s-stage that follows it."""
+        from ..ops.dispatch import dwf_fused_op
+        m = self.s_mats
+        t = self._tmp("pc_t", inp)
+        u = self._tmp("pc_u", inp)
+        if not dagger:
+            src = inp
+            if not self._b_is_identity:
+                self.apply_B(t, inp)                # t = B in  (even)
+                src = t
+            # u = B Ainv Dhat_oe t (odd); out = in - (1/4) Ainv Dhat_eo u
+            dwf_fused_op(u, src, self.gauge, 1, W=m["BAinv"])
+            dwf_fused_op(out, u, self.gauge, 0, W=m["Ainv"], a=-0.25,
+                         x=inp)
+        else:
+            self.apply_Ainv(t, inp, dagger=True)    # even
+            dwf_fused_op(u, t, self.gauge, 1, dagger=True,
+                         W=m["AinvdagBdag"])
+            W = None if self._b_is_identity else m["Bdag"]
+            dwf_fused_op(out, u, self.gauge, 0, dagger=True, W=W, a=-0.25,
+                         x=inp)
         return out
 
     def MdagM(self, out, inp, tmp):
@@ -185,13 +292,15 @@ class DiracMobiusPC(DiracMobius):
 class DiracDomainWall(DiracMobius):
     """Shamir DWF = Moebius(b5=1, c5=0) (ref: lib/dirac_domain_wall.cpp)."""
 
-    def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int):
-        super().__init__(gauge, mf, m5, Ls, b5=1.0, c5=0.0)
+    def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int,
+                 fused: Optional[bool] = None):
+        super().__init__(gauge, mf, m5, Ls, b5=1.0, c5=0.0, fused=fused)
 
 
 class DiracDomainWallPC(DiracMobiusPC):
-    def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int):
-        super().__init__(gauge, mf, m5, Ls, b5=1.0, c5=0.0)
+    def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int,
+                 fused: Optional[bool] = None):
+        super().__init__(gauge, mf, m5, Ls, b5=1.0, c5=0.0, fused=fused)
 
 
 class DiracZMobius(DiracMobius):
@@ -201,6 +310,8 @@ class DiracZMobius(DiracMobius):
 
       A_s = 1 + b5[s](4 - M5),  B hop = c5[s];  M = A - (1/2) Dhat B
     """
+
+    _fused_capable = False  # complex per-slice coefficients: unfused path
 
     def __init__(self, gauge: GaugeField, mf: float, m5: float, Ls: int,
                  b5, c5):
@@ -254,6 +365,8 @@ class DiracMobiusEofa(DiracMobius):
     det-ratio pseudofermion wiring is layered above these operators).
     The inverse applies one host-folded Sherman-Morrison correction on
     top of the O(Ls) M5 inverse."""
+
+    _fused_capable = False  # rank-1 extended A: unfused path
 
     def __init__(self, gauge: GaugeField, m5: float, Ls: int,
                  b5: float = 1.5, c5: float = 0.5, *, mq1: float = 0.01,

@@ -809,6 +809,79 @@ def dslash_wilson_slices(out: SpinorField, inp: SpinorField,
     return out
 
 
+DWF_FUSED_LS_MAX = 16  # csrc/launchers.h QA_DWF_FUSED_LS_MAX
+
+
+def dwf_fused_supported(out: SpinorField, gauge: GaugeField) -> bool:
+    """True where the fused domain-wall kernel (csrc/dslash_dwf_fused.h)
+    applies: GPU fields, no partitioned dimension, Ls <= 16, double/single/
+    half with reconstruct 18 (or 12 below double)."""
+    from ..parallel import comms
+    if out.device.type != "cuda" or gauge.device.type != "cuda":
+        return False
+    if comms.comm_mask() != 0:
+        return False
+    if not 1 <= out.ls <= DWF_FUSED_LS_MAX:
+        return False
+    if out.precision not in ("double", "single", "half"):
+        return False
+    if gauge.precision != out.precision:
+        return False
+    recon = RECON_COMPS[gauge.reconstruct]
+    return recon == 18 or (recon == 12 and out.precision != "double")
+
+
+def dwf_fused_op(out: SpinorField, inp: SpinorField, gauge: GaugeField,
+                 parity: int, dagger: bool = False, W=None, a: float = 1.0,
+                 x: Optional[SpinorField] = None):
+    """4-d hop of all Ls slices plus a dense per-chirality s-stage:
+
+        out(s) = [x(s) +] a * sum_s' W_chi[s, s'] (Dhat in)(s')
+
+    out/x at `parity`, in at the opposite parity (5-d single-parity
+    fields). W: real float64 [2, Ls, Ls] (upper block spins 0,1; lower
+    block spins 2,3) or None for the identity. One kernel launch where
+    dwf_fused_supported(); elsewhere (CPU, partitioned runs, Ls > 16) the
+    same result is composed from dslash_wilson_slices and the dense oracle
+    stage. out may alias x, never in."""
+    Ls = inp.ls
+    geo = out.geo
+    assert out.ls == Ls and out.n_parity == 1 and inp.n_parity == 1
+    assert out is not inp and out.data.data_ptr() != inp.data.data_ptr(), \
+        "dwf_fused_op: out must not alias in"
+    Wt = None
+    if W is not None:
+        Wt = torch.as_tensor(W, dtype=torch.float64).cpu().contiguous()
+        assert tuple(Wt.shape) == (2, Ls, Ls), (tuple(Wt.shape), Ls)
+    native = dwf_fused_supported(out, gauge)
+    trace_record("dwf_fused",
+                 f"{geo.dims}/Ls{Ls}/p{parity}/dag{int(dagger)}/"
+                 f"W{int(W is not None)}/x{int(x is not None)}/"
+                 f"{inp.precision}/{'native' if native else 'composed'}")
+    if native:
+        ext = hip_ext()
+        xf = x if x is not None else out
+        ext.dwf_fused(out.data, norm_or_empty(out), inp.data,
+                      norm_or_empty(inp), gauge.data, xf.data,
+                      norm_or_empty(xf), Wt, list(geo.dims),
+                      geo.parity_offset, geo.volume_cb, Ls, parity,
+                      bool(dagger), x is not None, float(a),
+                      RECON_COMPS[gauge.reconstruct])
+        return out
+    h = dwf_halo_exchange(inp, 1 - parity, dagger)
+    if Wt is None:
+        dslash_wilson_slices(out, inp, gauge, parity, dagger, a=a, x=x,
+                             halo=h)
+        return out
+    tmp = out.clone_empty()
+    dslash_wilson_slices(tmp, inp, gauge, parity, dagger, halo=h)
+    res = a * ref.apply_s_matrix(tmp.to_complex()[0], Ls, Wt)
+    if x is not None:
+        res = x.to_complex()[0] + res
+    out.from_complex(res.unsqueeze(0))
+    return out
+
+
 def dslash_wilson_slice(out: SpinorField, inp: SpinorField, gauge: GaugeField,
                         parity: int, s: int, dagger: bool = False,
                         a: float = 1.0, x: Optional[SpinorField] = None,

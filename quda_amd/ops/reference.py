@@ -331,6 +331,20 @@ def _m5_matrix(Ls, alpha, beta, mf, upper: bool, dagger: bool):
     return A
 
 
+def apply_s_matrix(psi5: torch.Tensor, Ls: int, W) -> torch.Tensor:
+    """[Ls*V, 4, 3] -> per-site dense s-space map: W[0] ([Ls, Ls] real) on
+    the upper chirality block (spins 0,1), W[1] on the lower (spins 2,3)."""
+    V = psi5.shape[0] // Ls
+    v = psi5.reshape(Ls, V, 4, 3)
+    Wt = torch.as_tensor(W, dtype=torch.float64).to(device=psi5.device,
+                                                    dtype=psi5.dtype)
+    out = torch.empty_like(v)
+    for blk, sl in ((0, slice(0, 2)), (1, slice(2, 4))):
+        out[:, :, sl, :] = torch.einsum("st,tvxc->svxc", Wt[blk],
+                                        v[:, :, sl, :])
+    return out.reshape(Ls * V, 4, 3)
+
+
 def m5inv(psi5: torch.Tensor, Ls: int, alpha: float, beta: float, mf: float,
           dagger: bool = False) -> torch.Tensor:
     """(alpha + beta Ds)^{-1} psi via dense per-chirality [Ls,Ls] solves."""
