@@ -65,9 +65,16 @@ static void dslash_wilson(at::Tensor out, at::Tensor out_n, at::Tensor in,
                           std::vector<at::Tensor> ghost_nrm,
                           std::vector<int64_t> face_cb, int64_t comm_mask,
                           int64_t kt, double b_re, double b_im,
-                          int64_t v_stride, int64_t s_offset) {
+                          int64_t v_stride, int64_t s_offset,
+                          c10::optional<at::Tensor> out2,
+                          c10::optional<at::Tensor> out2_n,
+                          c10::optional<at::Tensor> dot_y,
+                          c10::optional<at::Tensor> dot_y_n,
+                          c10::optional<at::Tensor> dot_result,
+                          int64_t dot_slots, int64_t dot_stride) {
   // v_stride: chunk stride of the spinor fields (Ls*Vcb for 5-d fields);
   // s_offset: site offset of the 4-d slice being operated on (s*Vcb)
+  // out2 / dot_y + dot_result: fused epilogues (launchers.h DslashCall)
   TORCH_CHECK(out.is_contiguous() && in.is_contiguous() && gauge.is_contiguous());
   if (v_stride == 0) v_stride = Vcb;
   DslashCall c{};
@@ -97,6 +104,36 @@ static void dslash_wilson(at::Tensor out, at::Tensor out_n, at::Tensor in,
   c.b_re = b_re;
   c.b_im = b_im;
   c.recon = (int)recon;
+  if (out2) {
+    TORCH_CHECK(out2_n && out2->is_contiguous() &&
+                out2->scalar_type() == out.scalar_type() &&
+                out2->numel() == out.numel() &&
+                out2->data_ptr() != out.data_ptr() &&
+                out2->data_ptr() != in.data_ptr(),
+                "dslash_wilson: out2 must be a distinct field shaped like out");
+    c.out2 = field_of_off(*out2, *out2_n, v_stride, s_offset);
+  }
+  if (dot_y) {
+    TORCH_CHECK(dot_y_n && dot_result && dot_y->is_contiguous() &&
+                dot_y->scalar_type() == out.scalar_type() &&
+                dot_y->numel() == out.numel(),
+                "dslash_wilson: dot_y must be a field shaped like out");
+    TORCH_CHECK(dot_slots >= 1 && dot_stride >= 1 &&
+                dot_result->scalar_type() == at::kDouble &&
+                dot_result->numel() >= (dot_slots - 1) * dot_stride + 1 &&
+                dot_result->is_contiguous() &&
+                dot_result->device() == out.device(),
+                "dslash_wilson: dot_result must be a float64 tensor on the "
+                "fields' device");
+    c.y = field_of_off(*dot_y, *dot_y_n, v_stride, s_offset);
+    c.dot_result = dot_result->data_ptr<double>();
+    c.dot_slots = (int)dot_slots;
+    c.dot_stride = (int)dot_stride;
+  }
+  TORCH_CHECK(qa_dslash_epilogue_ok(c),
+              "dslash_wilson: no fused-epilogue kernel for this launch (out2: "
+              "CLOV_POST, no dagger; dot: dagger PLAIN xpay; kt 0 or 1; "
+              "default occupancy form)");
   switch (prec_of(out)) {
     case 0: launch_dslash_wilson_double(c, stream()); break;
     case 1: launch_dslash_wilson_single(c, stream()); break;
@@ -256,6 +293,9 @@ static at::Tensor blas_op(int64_t op, double a, double b, at::Tensor x,
                           c10::optional<at::Tensor> z_n = c10::nullopt,
                           c10::optional<at::Tensor> w = c10::nullopt,
                           c10::optional<at::Tensor> w_n = c10::nullopt) {
+  TORCH_CHECK(op != BLAS_TRIPLE_CG_DEV,
+              "blas_op: BLAS_TRIPLE_CG_DEV takes a device accumulator — call "
+              "triple_cg_dev");
   BlasCall c{};
   c.op = (int)op;
   c.prec = prec_of(x);
@@ -288,6 +328,54 @@ static at::Tensor blas_op(int64_t op, double a, double b, at::Tensor x,
   check_launch("blas_op");
   if (reduction && deterministic) result = result.sum(0);
   return result;
+}
+
+// x += alpha p; r -= alpha Ap with alpha = r2_old / pAp formed on the
+// device; ||r||^2 accumulated into acc[1]; `clear` zeroed whole (see
+// k_triple_cg_dev). pAp = acc[0], or with `slots` non-empty the sum of
+// slots[s * slot_stride], s < nslots. All float64 on the fields' device.
+static void triple_cg_dev(double r2_old, at::Tensor acc, at::Tensor clear,
+                          at::Tensor p, at::Tensor p_n, at::Tensor Ap,
+                          at::Tensor Ap_n, at::Tensor x, at::Tensor x_n,
+                          at::Tensor r, at::Tensor r_n, int64_t Vcb,
+                          int64_t sites, int64_t ncomp, at::Tensor slots,
+                          int64_t nslots, int64_t slot_stride) {
+  auto ok = [&](const at::Tensor &t) {
+    return t.scalar_type() == at::kDouble && t.is_contiguous() &&
+           t.device() == p.device();
+  };
+  TORCH_CHECK(ok(acc) && acc.numel() >= 2,
+              "triple_cg_dev: acc must hold 2 float64 on the fields' device");
+  TORCH_CHECK(clear.numel() == 0 || ok(clear),
+              "triple_cg_dev: clear must be empty or float64 on the device");
+  if (clear.numel()) {
+    auto lo = (const char *)clear.data_ptr(), hi = lo + clear.numel() * 8;
+    auto a0 = (const char *)acc.data_ptr();
+    TORCH_CHECK(a0 + 16 <= lo || a0 >= hi,
+                "triple_cg_dev: clear must not overlap acc");
+  }
+  TORCH_CHECK(nslots == 0 ||
+              (ok(slots) && nslots >= 1 && nslots <= 64 && slot_stride >= 1 &&
+               slots.numel() >= (nslots - 1) * slot_stride + 1),
+              "triple_cg_dev: slots must hold nslots <= 64 strided float64");
+  BlasCall c{};
+  c.op = BLAS_TRIPLE_CG_DEV;
+  c.prec = prec_of(p);
+  c.a = r2_old;
+  c.ncomp = (int)ncomp;
+  c.x = field_of(p, p_n, Vcb);
+  c.y = field_of(Ap, Ap_n, Vcb);
+  c.z = field_of(x, x_n, Vcb);
+  c.w = field_of(r, r_n, Vcb);
+  c.sites = sites;
+  c.result = acc.data_ptr<double>();
+  c.clear = clear.numel() ? clear.data_ptr<double>() : nullptr;
+  c.clear_n = clear.numel();
+  c.nslots = (int)nslots;
+  c.slot_stride = (int)slot_stride;
+  c.slots = nslots ? slots.data_ptr<double>() : nullptr;
+  launch_blas(c, stream());
+  check_launch("triple_cg_dev");
 }
 
 static void convert(at::Tensor dst, at::Tensor dst_n, at::Tensor src,
@@ -531,6 +619,9 @@ static void set_dslash_waves(int64_t w) {
 }
 
 static void set_dslash_lds(int64_t v) { qa_dslash_lds_ref() = (int)v; }
+static int64_t get_dslash_block() { return qa_dslash_block(); }
+static int64_t get_dslash_lds() { return qa_dslash_lds(); }
+static int64_t get_dslash_waves() { return qa_dslash_waves(); }
 
 static void set_dwf_fused_ns(int64_t v) {
   if (v == 16 || v == 32) qa_dwf_fused_ns_ref() = (int)v;
@@ -703,7 +794,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("xpay"), py::arg("a"), py::arg("recon"), py::arg("ghost"),
         py::arg("ghost_nrm"), py::arg("face_cb"), py::arg("comm_mask"),
         py::arg("kt"), py::arg("b_re") = 0.0, py::arg("b_im") = 0.0,
-        py::arg("v_stride") = 0, py::arg("s_offset") = 0);
+        py::arg("v_stride") = 0, py::arg("s_offset") = 0,
+        py::arg("out2") = py::none(), py::arg("out2_n") = py::none(),
+        py::arg("dot_y") = py::none(), py::arg("dot_y_n") = py::none(),
+        py::arg("dot_result") = py::none(), py::arg("dot_slots") = 1,
+        py::arg("dot_stride") = 1);
   m.def("pack_face", &pack_face, "halo face pack (spin-projected)",
         py::arg("dst"), py::arg("dst_nrm"), py::arg("in"), py::arg("in_n"),
         py::arg("dims"), py::arg("parity_offset"), py::arg("Vcb"),
@@ -735,6 +830,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_dslash_lds", &set_dslash_lds,
         "LDS-tiled dslash policy: 1 = stage the in-spinor halo tile in LDS "
         "(half/quarter, local, tile-divisible dims)");
+  m.def("get_dslash_block", &get_dslash_block, "current dslash workgroup size");
+  m.def("get_dslash_lds", &get_dslash_lds, "current LDS-tiled dslash policy");
+  m.def("get_dslash_waves", &get_dslash_waves, "current occupancy variant");
   m.def("ipc_get_handle", &ipc_get_handle, "hipIpcGetMemHandle of a tensor");
   m.def("ipc_open_handle", &ipc_open_handle, "open a peer IPC handle");
   m.def("ipc_close_handle", &ipc_close_handle, "close a peer IPC mapping");
@@ -762,6 +860,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ncomp") = 24, py::arg("deterministic") = false,
         py::arg("z") = py::none(), py::arg("z_n") = py::none(),
         py::arg("w") = py::none(), py::arg("w_n") = py::none());
+  m.def("triple_cg_dev", &triple_cg_dev,
+        "fused CG update with alpha = r2_old / acc[0] formed on the device",
+        py::arg("r2_old"), py::arg("acc"), py::arg("clear"), py::arg("p"),
+        py::arg("p_n"), py::arg("Ap"), py::arg("Ap_n"), py::arg("x"),
+        py::arg("x_n"), py::arg("r"), py::arg("r_n"), py::arg("Vcb"),
+        py::arg("sites"), py::arg("ncomp"),
+        py::arg("slots"), py::arg("nslots"), py::arg("slot_stride"));
   m.def("convert", &convert, "precision conversion copy", py::arg("dst"),
         py::arg("dst_n"), py::arg("src"), py::arg("src_n"), py::arg("Vcb"),
         py::arg("sites"), py::arg("ncomp") = 24);
@@ -782,6 +887,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("BLAS_SCAL") = (int)BLAS_SCAL;
   m.attr("BLAS_NORM2") = (int)BLAS_NORM2;
   m.attr("BLAS_TRIPLE_CG") = (int)BLAS_TRIPLE_CG;
+  m.attr("BLAS_TRIPLE_CG_DEV") = (int)BLAS_TRIPLE_CG_DEV;
   m.attr("BLAS_REDOT") = (int)BLAS_REDOT;
   m.attr("BLAS_CDOT") = (int)BLAS_CDOT;
   m.attr("BLAS_CAXPBY") = (int)BLAS_CAXPBY;

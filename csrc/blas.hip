@@ -6,40 +6,7 @@
 // half), reductions accumulate double.
 // Block 256 (4 waves), grid-stride; block-reduce -> one f64 atomic per block.
 #include "common.h"
-
-// ---------------------------------------------------------------------------
-// reduction plumbing
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_reduce(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// finish mode: per_block=false -> one f64 atomic per block (fast path);
-// per_block=true -> write partial[blockIdx] for a deterministic ordered
-// host/torch sum (ref: QUDA_DETERMINISTIC_REDUCE, comm_quda.h:204)
-__device__ __forceinline__ void block_atomic_add(double v, double *out,
-                                                 bool per_block = false,
-                                                 int slot_stride = 1,
-                                                 int slot = 0) {
-  __shared__ double partial[4];
-  int lane = threadIdx.x & 63;
-  int wave = threadIdx.x >> 6;
-  v = wave_reduce(v);
-  if (lane == 0) partial[wave] = v;
-  __syncthreads();
-  if (wave == 0) {
-    double s = (lane < (int)(blockDim.x >> 6)) ? partial[lane] : 0.0;
-    s = wave_reduce(s);
-    if (lane == 0) {
-      if (per_block)
-        out[(long)blockIdx.x * slot_stride + slot] = s;
-      else
-        atomicAdd(out + slot, s);
-    }
-  }
-}
+#include "reduce.h"
 
 #define GRID_STRIDE(g, n)                                                     \
   for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < (n);         \
@@ -246,6 +213,55 @@ __global__ __launch_bounds__(256) void k_triple_cg(
   block_atomic_add(acc, result, det, 2, 0);
 }
 
+// k_triple_cg with alpha formed on the device. acc = {pAp, ||r||^2} of this
+// iteration. pAp comes from the fused-dot dslash that ran before: either
+// acc[0] itself (nslots == 0), or the sum of slots[s * slot_stride],
+// s < nslots <= 64, which every wave forms in the same lane order, so all
+// threads hold the same value; the total is then also stored to acc[0] for
+// the host. Every thread forms alpha = (R)(r2_old / pAp), the value the host
+// would pass to k_triple_cg. pAp <= 0 (breakdown) leaves x and r untouched;
+// the host reads acc and stops. acc[1] must be zero on entry;
+// clear[0..clear_n) (the accumulator the NEXT iteration adds into, idle
+// while this kernel runs) is zeroed by the first wave with ordinary stores.
+template <typename A>
+__global__ __launch_bounds__(256) void k_triple_cg_dev(
+    double r2_old, double *acc_out, double *clear, long clear_n,
+    const double *slots, int nslots, int slot_stride, A p, A ap, A x, A r,
+    long sites) {
+  using R = typename A::R;
+  if (clear && blockIdx.x == 0 && threadIdx.x < 64)
+    for (long k = threadIdx.x; k < clear_n; k += 64) clear[k] = 0.0;
+  double pAp;
+  if (nslots > 0) {
+    int lane = threadIdx.x & 63;
+    double v = lane < nslots ? slots[(long)lane * slot_stride] : 0.0;
+    v = wave_reduce(v);
+    pAp = __shfl(v, 0, 64);
+    if (blockIdx.x == 0 && threadIdx.x == 0) acc_out[0] = pAp;
+  } else {
+    pAp = acc_out[0];
+  }
+  if (pAp <= 0.0) return;  // uniform over the whole grid
+  const R a = (R)(r2_old / pAp);
+  double acc = 0.0;
+  GRID_STRIDE(g, sites) {
+    cplx<R> pv[A::NCPLX], av[A::NCPLX], xv[A::NCPLX], rv[A::NCPLX];
+    p.load_v(pv, g);
+    ap.load_v(av, g);
+    x.load_v(xv, g);
+    r.load_v(rv, g);
+#pragma unroll
+    for (int k = 0; k < A::NCPLX; ++k) {
+      xv[k] = xv[k] + a * pv[k];
+      rv[k] = rv[k] - a * av[k];
+      acc += (double)rv[k].re * rv[k].re + (double)rv[k].im * rv[k].im;
+    }
+    x.store_v(xv, g);
+    r.store_v(rv, g);
+  }
+  block_atomic_add(acc, acc_out, false, 1, 1);
+}
+
 template <typename A>
 static void blas_dispatch(const BlasCall &c, hipStream_t st) {
   using S = typename A::S;
@@ -268,6 +284,14 @@ static void blas_dispatch(const BlasCall &c, hipStream_t st) {
       A w{(S *)c.w.data, (float *)c.w.norm, c.w.Vcb};
       hipLaunchKernelGGL((k_triple_cg<A>), dim3(gr), dim3(BLK), 0, st,
                          (R)c.a, x, y, z, w, n, c.result, c.det);
+      break;
+    }
+    case BLAS_TRIPLE_CG_DEV: {
+      A z{(S *)c.z.data, (float *)c.z.norm, c.z.Vcb};
+      A w{(S *)c.w.data, (float *)c.w.norm, c.w.Vcb};
+      hipLaunchKernelGGL((k_triple_cg_dev<A>), dim3(gr), dim3(BLK), 0, st,
+                         c.a, c.result, c.clear, c.clear_n, c.slots, c.nslots,
+                         c.slot_stride, x, y, z, w, n);
       break;
     }
     case BLAS_XPAY:

@@ -21,6 +21,7 @@ void launch_clover_apply(const CloverApplyCall &c, hipStream_t st) {
     case 0: clover_apply_t<PrecDouble>(c, st); break;
     case 1: clover_apply_t<PrecSingle>(c, st); break;
     case 2: clover_apply_t<PrecHalf>(c, st); break;
+    case 3: clover_apply_t<PrecQuarter>(c, st); break;
   }
 }
 

@@ -131,6 +131,53 @@ __device__ __forceinline__ void store_chunk(S *p, const S in[W]) {
 }
 
 // ---------------------------------------------------------------------------
+// storage round trip of one site (the ONE definition, behind
+// SpinorAcc::store_v / load_v and so behind every kernel's loads and stores).
+// quantize: has_norm precisions scale by the site max m (returned; the
+// per-site norm), the others cast and return 1. dequantize: scale * stored.
+// ---------------------------------------------------------------------------
+template <typename Prec, int NCPLX>
+__device__ __forceinline__ typename Prec::Real qa_quantize(
+    typename Prec::Store *tmp, const cplx<typename Prec::Real> *in) {
+  using S = typename Prec::Store;
+  using R = typename Prec::Real;
+  if constexpr (Prec::has_norm) {
+    R m = (R)0;
+#pragma unroll
+    for (int k = 0; k < NCPLX; ++k)
+      m = fmax(m, fmax(fabs(in[k].re), fabs(in[k].im)));
+    R inv = m > (R)0 ? (R)1 / m : (R)0;
+#pragma unroll
+    for (int k = 0; k < NCPLX; ++k) {
+      tmp[2 * k] = qa_tos<S>(in[k].re * inv);
+      tmp[2 * k + 1] = qa_tos<S>(in[k].im * inv);
+    }
+    return m;
+  } else {
+#pragma unroll
+    for (int k = 0; k < NCPLX; ++k) {
+      tmp[2 * k] = (S)in[k].re;
+      tmp[2 * k + 1] = (S)in[k].im;
+    }
+    return (R)1;
+  }
+}
+
+template <typename Prec, int NCPLX>
+__device__ __forceinline__ void qa_dequantize(
+    cplx<typename Prec::Real> *out, const typename Prec::Store *tmp,
+    typename Prec::Real scale) {
+  using S = typename Prec::Store;
+  using R = typename Prec::Real;
+#pragma unroll
+  for (int k = 0; k < NCPLX; ++k) {
+    R re, im;
+    qa_tor_pair<R, S>(tmp + 2 * k, re, im);
+    out[k] = {scale * re, scale * im};
+  }
+}
+
+// ---------------------------------------------------------------------------
 // spinor accessor: NCOMP reals/site in [NCOMP/CW][V][CW]; CW is the widest
 // chunk (<= Prec::W) dividing NCOMP (24 -> 16B chunks everywhere; staggered
 // 6 -> one complex per chunk, the reference's staggered FloatN choice)
@@ -169,36 +216,19 @@ struct SpinorAcc {
       load_chunk<S, W>(data + base + (long)ch * V * W, tmp + ch * W);
     R scale = (R)1;
     if constexpr (Prec::has_norm) scale = norm[g];
-#pragma unroll
-    for (int k = 0; k < NCPLX; ++k) {
-      R re, im;
-      qa_tor_pair<R, S>(tmp + 2 * k, re, im);
-      out[k] = {scale * re, scale * im};
-    }
+    qa_dequantize<Prec, NCPLX>(out, tmp, scale);
   }
 
   __device__ __forceinline__ void store_v(const cplx<R> in[NCPLX], long g) const {
     S tmp[NCOMP];
+    R m = qa_quantize<Prec, NCPLX>(tmp, in);
+    store_raw(tmp, m, g);
+  }
+
+  __device__ __forceinline__ void store_raw(const S tmp[NCOMP], R m,
+                                            long g) const {
     long base = chunk_base(g);
-    if constexpr (Prec::has_norm) {
-      R m = (R)0;
-#pragma unroll
-      for (int k = 0; k < NCPLX; ++k)
-        m = fmax(m, fmax(fabs(in[k].re), fabs(in[k].im)));
-      norm[g] = m;
-      R inv = m > (R)0 ? (R)1 / m : (R)0;
-#pragma unroll
-      for (int k = 0; k < NCPLX; ++k) {
-        tmp[2 * k] = qa_tos<S>(in[k].re * inv);
-        tmp[2 * k + 1] = qa_tos<S>(in[k].im * inv);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NCPLX; ++k) {
-        tmp[2 * k] = (S)in[k].re;
-        tmp[2 * k + 1] = (S)in[k].im;
-      }
-    }
+    if constexpr (Prec::has_norm) norm[g] = m;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch)
       store_chunk<S, W>(data + base + (long)ch * V * W, tmp + ch * W);

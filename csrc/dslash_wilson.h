@@ -15,6 +15,7 @@
 #include "common.h"
 #include "generated/proj.h"
 #include "halo.h"
+#include "reduce.h"
 
 // epilogue modes (b = (b_re, b_im) twist scalar, T(b) v = b_re v + i b_im g5 v):
 //   PLAIN      : out = [x +] a * (D in)
@@ -107,6 +108,15 @@ __device__ __forceinline__ void clover_mul(cplx<R> out[4][3], const R diag[2][6]
 // 2 waves/SIMD). LBW > 0: 64-thread workgroups with a minimum of LBW waves
 // per SIMD — caps the register allocation (512/LBW) to raise occupancy on
 // this latency-bound kernel (profiles/r01_dslash_pmc_analysis.md).
+//
+// The stencil itself lives in dslash_wilson_body.inl, shared with the two
+// fused-epilogue kernels below. They serve the two launches of
+// DiracCloverPC::MdagM whose output the next kernel would only re-read
+// (Q = the storage round trip of `out`, i.e. exactly what a later load of
+// the stored site returns):
+//   k_dslash_wilson_clov_out2 : also out2 = A_clov * Q(out) — the clover
+//       apply that opens M^dag, with the site matrix still in registers
+//   k_dslash_wilson_xpay_dot  : also *result += Re <y, Q(out)> (the CG's pAp)
 template <typename Prec, int RECON, bool DAG, int MODE, bool XPAY, int KT = KT_LOCAL,
           int LBW = 0>
 __global__ __launch_bounds__(LBW ? 64 : 256, LBW ? LBW : 1) void k_dslash_wilson(
@@ -117,184 +127,87 @@ __global__ __launch_bounds__(LBW ? 64 : 256, LBW ? LBW : 1) void k_dslash_wilson
   using R = typename Prec::Real;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.Vcb) return;
-  int xc[4];
-  coords_from_cb(xc, i, d, parity);
+#include "dslash_wilson_body.inl"
+  out.store(acc, i);
+}
 
-  cplx<R> acc[4][3];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[s][c] = {(R)0, (R)0};
+// CLOV_POST dslash that also writes out2 = A_clov * Q(out), Q = the storage
+// round trip of out (kt 0/1 only: boundary sites of the interior kernel
+// defer their epilogue to the exterior kernel). Like the dot kernel below it
+// exists in the default 256-thread-cap form only: under the 64-thread
+// occupancy experiment (QUDA_AMD_DSLASH_WAVES=3, which spills) the
+// operators keep the unfused launch sequence. `out` is bitwise what
+// k_dslash_wilson stores.
+template <typename Prec, int RECON, bool DAG, bool XPAY, int KT = KT_LOCAL>
+__global__ __launch_bounds__(256, 1) void k_dslash_wilson_clov_out2(
+    SpinorAcc<Prec> out, SpinorAcc<Prec> in, GaugeAcc<Prec, RECON> g,
+    CloverAcc<Prec> clov, LatDims d, int parity, typename Prec::Real a,
+    SpinorAcc<Prec> x, GhostAcc<Prec> gh, SpinorAcc<Prec> out2) {
+  using R = typename Prec::Real;
+  static_assert(KT == KT_LOCAL || KT == KT_FUSED);
+  constexpr int MODE = CLOV_POST;
+  constexpr int LBW = 0;
+  const R br = (R)0, bi = (R)0;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= d.Vcb) return;
+  // the CLOV_POST site matrix outlives the body: it is applied once more
+  R diag[2][6];
+  cplx<R> tri[2][15];
+#define QA_DSLASH_CLOVER_DECLARED
+#include "dslash_wilson_body.inl"
+#undef QA_DSLASH_CLOVER_DECLARED
+  // q = the site as re-loaded after the store, behind a compiler barrier:
+  // see k_dslash_wilson_xpay_dot for why it is not taken from the registers
+  out.store(acc, i);
+  asm volatile("" ::: "memory");
+  cplx<R> q[4][3], aq[4][3];
+  out.load(q, i);
+  clover_mul(aq, diag, tri, q);
+  out2.store(aq, i);
+}
 
-  cplx<R> p[4][3], h[8][2][3], uh[2][3], U[3][3];
-  // proj/recon tables encode 2P (generate_proj.py); the stencil needs P
-  const R one = (R)0.5;
-
-  bool bnd = false;  // interior: site has >=1 hop deferred to EXTERIOR
-  if constexpr (KT == KT_INTERIOR) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      if (gh.active(m) && (xc[m] == 0 || xc[m] == d.X[m] - 1)) bnd = true;
-  }
-  bool skip[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) skip[k] = false;
-  // -mu neighbor index, kept for phase 2: the backward link U_mu(x-mu) is
-  // read from the NEIGHBOR's forward slot instead of this site's bwd slot.
-  // The stencil layout stores every link twice (fwd slot of x == bwd slot
-  // of x+mu); reading only fwd slots halves the dslash's UNIQUE gauge
-  // traffic — neighbor fwd-slot lines are shared through L2 exactly like
-  // the neighbor spinor loads. Boundary-crossing hops (jm < 0) still read
-  // the bwd slot, which holds the -mu RANK's link from the load-time
-  // exchange (fields/gauge.py from_complex).
-  long jm[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) jm[k] = -1;
-
-  // Phase 1: gather + spin-project all 8 neighbor half-spinors first — the
-  // loads are independent, so the wave has 8 spinor fetches in flight
-  // instead of a serialized load->project->multiply chain per direction
-  // (the dslash is latency-bound at ~30% of HBM peak otherwise; measured
-  // FETCH_SIZE is already near-minimal).
-#define QA_GATHER(MU)                                                     \
-  {                                                                       \
-    bool cross_p = KT != KT_LOCAL && gh.active(MU) && xc[MU] == d.X[MU] - 1; \
-    if (KT == KT_INTERIOR && cross_p) {                                   \
-      skip[2 * MU] = true;                                                \
-    } else if (KT == KT_FUSED && cross_p) {                               \
-      gh.load(h[2 * MU], MU, 1, ghost_idx(xc, MU, d));                    \
-    } else {                                                              \
-      long j = neighbor_cb(xc, MU, +1, d);                                \
-      in.load(p, j);                                                      \
-      if constexpr (!DAG) proj_##MU##_0(h[2 * MU], p);                    \
-      else proj_##MU##_1(h[2 * MU], p);                                   \
-    }                                                                     \
-    bool cross_m = KT != KT_LOCAL && gh.active(MU) && xc[MU] == 0;        \
-    if (KT == KT_INTERIOR && cross_m) {                                   \
-      skip[2 * MU + 1] = true;                                            \
-    } else if (KT == KT_FUSED && cross_m) {                               \
-      gh.load(h[2 * MU + 1], MU, 0, ghost_idx(xc, MU, d));                \
-    } else {                                                              \
-      long j = neighbor_cb(xc, MU, -1, d);                                \
-      jm[MU] = j;                                                         \
-      in.load(p, j);                                                      \
-      if constexpr (!DAG) proj_##MU##_1(h[2 * MU + 1], p);                \
-      else proj_##MU##_0(h[2 * MU + 1], p);                               \
-    }                                                                     \
-  }
-
-  // Phase 2 macro: gauge multiplies + spin reconstruction (fwd link at own
-  // site; bwd link from the -mu neighbor's fwd slot, see jm above)
-#define QA_MUL(MU)                                                        \
-  {                                                                       \
-    if (!skip[2 * MU]) {                                                  \
-      g.template load<MU>(U, i);                                          \
-      su3_mul_half(uh, U, h[2 * MU]);                                     \
-      if constexpr (!DAG) recon_##MU##_0(acc, uh, one);                   \
-      else recon_##MU##_1(acc, uh, one);                                  \
-    }                                                                     \
-    if (!skip[2 * MU + 1]) {                                              \
-      if (jm[MU] >= 0) g.template load_o<MU>(U, jm[MU]);                  \
-      else g.template load<4 + MU>(U, i);                                 \
-      su3_dagmul_half(uh, U, h[2 * MU + 1]);                              \
-      if constexpr (!DAG) recon_##MU##_1(acc, uh, one);                   \
-      else recon_##MU##_0(acc, uh, one);                                  \
-    }                                                                     \
-  }
-
-  if constexpr (LBW == 0) {
-    // all 8 gathers in flight, then all multiplies (max load ILP; ~210
-    // VGPRs -> 2 waves/SIMD)
-    QA_GATHER(0)
-    QA_GATHER(1)
-    QA_GATHER(2)
-    QA_GATHER(3)
-    QA_MUL(0)
-    QA_MUL(1)
-    QA_MUL(2)
-    QA_MUL(3)
-  } else {
-    // split-gather: two 4-neighbor rounds halve the live half-spinor
-    // state so the LBW-wave occupancy cap is met without spilling —
-    // trades per-wave ILP for thread-level parallelism.
-    QA_GATHER(0)
-    QA_GATHER(1)
-    QA_MUL(0)
-    QA_MUL(1)
-    // pin the round split: without this the scheduler hoists round-2 loads
-    // into round 1 and the live state spills right back to the 8-gather shape
-    __builtin_amdgcn_sched_barrier(0);
-    QA_GATHER(2)
-    QA_GATHER(3)
-    QA_MUL(2)
-    QA_MUL(3)
-  }
-#undef QA_GATHER
-#undef QA_MUL
-
-  // boundary sites under CLOV_POST defer the whole epilogue: store raw sum
-  if constexpr (KT == KT_INTERIOR && MODE == CLOV_POST) {
-    if (bnd) {
-      out.store(acc, i);
-      return;
-    }
-  }
-
-  if constexpr (MODE == CLOV_POST) {
-    R diag[2][6];
-    cplx<R> tri[2][15];
-    clov.load(diag, tri, parity, i);
-    cplx<R> tmp[4][3];
-    clover_mul(tmp, diag, tri, acc);
+// PLAIN xpay dslash that also accumulates Re <y, Q(out)> (kt 0/1 only).
+// The stencil, the epilogue and the store are those of k_dslash_wilson, so
+// `out` is bitwise what that kernel stores: the dot is formed from the site
+// as RE-LOADED after the store (this thread's own write), behind a compiler
+// barrier — feeding the dot from the registers instead changes the packed-
+// math / FMA-contraction pattern the compiler picks for the whole stencil.
+// Workgroup b adds its partial sum into result[(b % nslots) * stride]: with
+// one word, the 16384 same-address f64 atomics of a 32^3x64 launch at 64
+// threads per workgroup serialise and the kernel that reads the sum waits
+// for them; the consumer adds the slots up (k_triple_cg_dev).
+// No early return: every thread of the block reaches the reduction's
+// __syncthreads(); threads past the last site skip the stencil and add 0.
+template <typename Prec, int RECON, bool DAG, int KT = KT_LOCAL>
+__global__ __launch_bounds__(256, 1) void k_dslash_wilson_xpay_dot(
+    SpinorAcc<Prec> out, SpinorAcc<Prec> in, GaugeAcc<Prec, RECON> g,
+    CloverAcc<Prec> clov, LatDims d, int parity, typename Prec::Real a,
+    SpinorAcc<Prec> x, GhostAcc<Prec> gh, SpinorAcc<Prec> y, double *result,
+    int nslots, int stride) {
+  using R = typename Prec::Real;
+  static_assert(KT == KT_LOCAL || KT == KT_FUSED);
+  constexpr int MODE = PLAIN;
+  constexpr bool XPAY = true;
+  constexpr int LBW = 0;
+  const R br = (R)0, bi = (R)0;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  double dot = 0.0;
+  if (i < d.Vcb) {
+#include "dslash_wilson_body.inl"
+    out.store(acc, i);
+    asm volatile("" ::: "memory");
+    cplx<R> q[4][3], yv[4][3];
+    out.load(q, i);
+    y.load(yv, i);
+    // same per-site order as k_reduce<A, 1>(y, out)
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) acc[s][c] = tmp[s][c];
+      for (int c = 0; c < 3; ++c)
+        dot += (double)yv[s][c].re * q[s][c].re +
+               (double)yv[s][c].im * q[s][c].im;
   }
-  if constexpr (MODE == TWIST_POST) twist_mul(acc, br, bi);
-
-  if constexpr (XPAY || MODE == CLOV_X || MODE == TWIST_X || MODE == CLOVTW_X) {
-    cplx<R> xv[4][3];
-    x.load(xv, i);
-    if constexpr (MODE == CLOV_X || MODE == CLOVTW_X) {
-      R diag[2][6];
-      cplx<R> tri[2][15];
-      clov.load(diag, tri, parity, i);
-      cplx<R> Ax[4][3];
-      clover_mul(Ax, diag, tri, xv);
-      if constexpr (MODE == CLOVTW_X) {
-        twist_mul(xv, (R)0, bi);  // i b_im g5 x
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) Ax[s][c] += xv[s][c];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[s][c] = Ax[s][c] + a * acc[s][c];
-    } else if constexpr (MODE == TWIST_X) {
-      twist_mul(xv, br, bi);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[s][c] = xv[s][c] + a * acc[s][c];
-    } else {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[s][c] = xv[s][c] + a * acc[s][c];
-    }
-  } else {
-    if (a != (R)1) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[s][c] = a * acc[s][c];
-    }
-  }
-
-  out.store(acc, i);
+  block_atomic_add(dot, result + (long)(blockIdx.x % (unsigned)nslots) * stride);
 }
 
 // EXTERIOR: one owner thread per boundary site adds all ghost-hop

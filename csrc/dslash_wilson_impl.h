@@ -38,6 +38,38 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
   int waves = qa_dslash_waves();
   int grid64 = (int)((c.Vcb + 63) / 64);
 
+  // fused-epilogue kernels (k_dslash_wilson_clov_out2 / _xpay_dot): dispatched
+  // apart from the QA_MODES matrix so only the combinations MdagM uses are
+  // instantiated — CLOV_POST x {xpay, no xpay} with out2, dagger PLAIN xpay
+  // with dot; kt 0/1, default occupancy form only. The caller checked
+  // qa_dslash_epilogue_ok.
+  if (c.out2.data || c.y.data) {
+    SpinorAcc<Prec> out2{(typename Prec::Store *)c.out2.data, (float *)c.out2.norm, c.out2.Vcb};
+    SpinorAcc<Prec> y{(typename Prec::Store *)c.y.data, (float *)c.y.norm, c.y.Vcb};
+#define QA_EPI_LAUNCH(KERNEL, KT, ...)                                         \
+  hipLaunchKernelGGL((KERNEL<Prec, RECON, __VA_ARGS__, KT>), dim3(grid),       \
+                     dim3(blk), 0, st, out, in, g, cl, d, c.parity, a, x, gh,  \
+                     QA_EPI_TAIL)
+    if (c.out2.data) {
+#define QA_EPI_TAIL out2
+      if (c.kt == 0) {
+        if (c.xpay) { QA_EPI_LAUNCH(k_dslash_wilson_clov_out2, KT_LOCAL, false, true); }
+        else { QA_EPI_LAUNCH(k_dslash_wilson_clov_out2, KT_LOCAL, false, false); }
+      } else {
+        if (c.xpay) { QA_EPI_LAUNCH(k_dslash_wilson_clov_out2, KT_FUSED, false, true); }
+        else { QA_EPI_LAUNCH(k_dslash_wilson_clov_out2, KT_FUSED, false, false); }
+      }
+#undef QA_EPI_TAIL
+    } else {
+#define QA_EPI_TAIL y, c.dot_result, c.dot_slots, c.dot_stride
+      if (c.kt == 0) { QA_EPI_LAUNCH(k_dslash_wilson_xpay_dot, KT_LOCAL, true); }
+      else { QA_EPI_LAUNCH(k_dslash_wilson_xpay_dot, KT_FUSED, true); }
+#undef QA_EPI_TAIL
+    }
+#undef QA_EPI_LAUNCH
+    return;
+  }
+
   // LDS-tiled path (half/quarter, local, 4-d, tile-divisible dims,
   // PLAIN/CLOV_POST/TWIST_POST): see k_dslash_wilson_lds
   if constexpr (Prec::has_norm) {

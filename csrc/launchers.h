@@ -59,6 +59,10 @@ enum BlasOp {
   BLAS_CDOT,
   BLAS_CAXPBY,
   BLAS_TRIPLE_CG,  // x += a p; r -= a Ap; -> ||r||^2 (ref tripleCGUpdate)
+  // same update with alpha = a / result[0] formed on the device (a = the
+  // host's r2_old, result[0] = pAp from the fused-dot dslash); ||r||^2 is
+  // accumulated into result[1]; `clear` = the next iteration's accumulator
+  BLAS_TRIPLE_CG_DEV,
 };
 
 struct BlasCall {
@@ -72,6 +76,13 @@ struct BlasCall {
   int ncomp;     // reals per site: 24 (Wilson) or 6 (staggered)
   bool det;      // deterministic reduce: result = per-block partials
   double *result;  // device ptr (2 doubles, or [grid][2] partials if det)
+  // TRIPLE_CG_DEV: pAp = result[0], or, with nslots > 0, the sum of
+  // slots[s * slot_stride], s < nslots <= 64 (then also written to
+  // result[0]); clear[0..clear_n) is zeroed by the kernel (null = nothing)
+  double *clear;
+  long clear_n;
+  const double *slots;
+  int nslots, slot_stride;
 };
 
 void launch_blas(const BlasCall &c, hipStream_t st);
@@ -101,7 +112,26 @@ struct DslashCall {
   long face_cb[4];
   int comm_mask;
   int kt;  // 0 local, 1 fused, 2 interior, 3 exterior (csrc/dslash_wilson.h)
+  // fused epilogues (kt 0/1 only, never both at once; null = off):
+  //   out2       : CLOV_POST, !dagger: out2 = A_clov * (out as stored)
+  //   y + result : dagger PLAIN xpay: Re <y, out as stored> is added into
+  //                dot_result, workgroup b into word (b % dot_slots) * dot_stride
+  BlasField out2, y;
+  double *dot_result;
+  int dot_slots, dot_stride;
 };
+
+// true where the fused-epilogue request in c has a compiled kernel
+inline bool qa_dslash_epilogue_ok(const DslashCall &c) {
+  if (!c.out2.data && !c.y.data) return true;
+  if (c.kt != 0 && c.kt != 1) return false;
+  if (qa_dslash_waves() != 0) return false;  // default occupancy form only
+  if (c.y.data && (c.dot_slots < 1 || c.dot_stride < 1)) return false;
+  if (c.out2.data && c.y.data) return false;
+  if (c.out2.data) return c.mode == 1 && !c.dagger;
+  if (c.y.data) return c.mode == 0 && c.dagger && c.xpay && c.dot_result;
+  return true;
+}
 
 void launch_dslash_wilson_double(const DslashCall &c, hipStream_t st);
 void launch_dslash_wilson_single(const DslashCall &c, hipStream_t st);

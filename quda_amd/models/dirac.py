@@ -21,7 +21,8 @@ from ..fields.clover import CloverField
 from ..fields.gauge import GaugeField
 from ..fields.spinor import SpinorField
 from ..ops import blas
-from ..ops.dispatch import CLOV_POST, CLOV_X, PLAIN, apply_clover, dslash_wilson
+from ..ops.dispatch import (CLOV_POST, CLOV_X, PLAIN, apply_clover,
+                            dslash_wilson, fused_epilogue_ok, on_gpu)
 
 
 class Dirac:
@@ -34,9 +35,10 @@ class Dirac:
         self._tmps = {}
 
     def dslash(self, out, inp, parity, dagger=False, mode=PLAIN, a=1.0,
-               x=None, clover=None, clover_inverse=False, twist=(0.0, 0.0)):
+               x=None, clover=None, clover_inverse=False, twist=(0.0, 0.0),
+               **epilogue):
         return dslash_wilson(out, inp, self.gauge, parity, dagger, mode, a, x,
-                             clover, clover_inverse, twist)
+                             clover, clover_inverse, twist, **epilogue)
 
     def tmp(self, name: str, like: SpinorField, n_parity=1) -> SpinorField:
         key = (name, like.precision, str(like.device), n_parity)
@@ -160,8 +162,57 @@ class DiracCloverPC(Dirac, _CloverMixin):
         return out
 
     def MdagM(self, out, inp, tmp):
-        self.M(tmp, inp, dagger=False)
-        self.M(out, tmp, dagger=True)
+        """out = M^dag M inp. Where the dslash takes fused epilogues, the
+        launch that ends M also writes A_ee^-1 tmp — the clover apply that
+        opens M^dag — so the product is 4 launches, not 5; the values are
+        those of M followed by M(dagger=True)."""
+        return self._MdagM(out, inp, tmp, None)
+
+    def MdagM_dot(self, out, inp, tmp, result, slots=1, stride=1):
+        """MdagM that also adds Re <inp, out> (out as stored) into result, a
+        float64 tensor on the fields' device that the caller zeroes: on the
+        GPU the dot rides in the epilogue of the last dslash instead of a
+        reduction kernel re-reading both fields. `out` is bitwise that of
+        MdagM. With slots > 1 the partial sums are spread over the words
+        result[s * stride], s < slots, and the dot is their sum (many
+        atomics on one word serialise)."""
+        return self._MdagM(out, inp, tmp, result, slots, stride)
+
+    def _MdagM(self, out, inp, tmp, result, slots=1, stride=1):
+        # a subclass that redefines M (distance / Hasenbusch-twist
+        # preconditioning) composes MdagM from ITS M
+        own_m = type(self).M is DiracCloverPC.M
+        if not (own_m and fused_epilogue_ok(out, inp)):
+            self.M(tmp, inp, dagger=False)
+            self.M(out, tmp, dagger=True)
+            if result is not None and not on_gpu(out, inp):
+                result[0] += blas.re_dot(inp, out)
+            elif result is not None:
+                from ..ops.dispatch import hip_ext, norm_or_empty
+                ext = hip_ext()
+                r = ext.blas_op(ext.BLAS_REDOT, 0.0, 0.0, inp.data,
+                                norm_or_empty(inp), out.data,
+                                norm_or_empty(out), inp.volume_cb,
+                                inp.n_parity * inp.volume_cb, ncomp=inp.ncomp)
+                result[:1].add_(r[:1])
+            return out
+        k2 = -self.kappa ** 2
+        t0 = self.tmp("pc_even", inp)
+        t1 = self.tmp("pc_odd", inp)
+        # M, its last launch also storing t0 = A_ee^-1 tmp
+        self.dslash(t1, inp, 1, mode=CLOV_POST, clover=self.clover,
+                    clover_inverse=True)
+        self.dslash(tmp, t1, 0, mode=CLOV_POST, a=k2, x=inp,
+                    clover=self.clover, clover_inverse=True, out2=t0)
+        # M^dag = 1 - k^2 D_oe^dag A_oo^-1 D_eo^dag A_ee^-1, A_ee^-1 done
+        self.dslash(t1, t0, 1, dagger=True, mode=CLOV_POST,
+                    clover=self.clover, clover_inverse=True)
+        if result is None:
+            self.dslash(out, t1, 0, dagger=True, a=k2, x=tmp)
+        else:
+            self.dslash(out, t1, 0, dagger=True, a=k2, x=tmp,
+                        dot_with=inp, dot_result=result, dot_slots=slots,
+                        dot_stride=stride)
         return out
 
     def prepare(self, b_full: SpinorField) -> SpinorField:

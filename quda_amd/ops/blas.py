@@ -131,6 +131,29 @@ def triple_cg_update(a: float, p: SpinorField, Ap: SpinorField,
     return axpy_norm2(-a, Ap, r)
 
 
+def triple_cg_update_dev(r2_old: float, acc: torch.Tensor, clear,
+                         p: SpinorField, Ap: SpinorField, x: SpinorField,
+                         r: SpinorField, slots=None, nslots: int = 0,
+                         slot_stride: int = 1) -> None:
+    """triple_cg_update with alpha = r2_old / pAp formed on the device (GPU
+    fields only). acc: 2 float64 on the device, acc[1] = 0 on entry and
+    ||r||^2 on return. pAp is acc[0], or, with nslots > 0, the sum of
+    slots[s * slot_stride], s < nslots <= 64 as left by
+    DiracCloverPC.MdagM_dot, which the kernel also stores to acc[0].
+    pAp <= 0 leaves x and r unchanged. clear: float64 tensor that the kernel
+    zeroes whole (the next iteration's accumulator), or None. Nothing is read
+    back: the caller fetches acc when it needs the values."""
+    assert on_gpu(p, Ap, x, r), "triple_cg_update_dev: GPU fields only"
+    ext = hip_ext()
+    empty = torch.empty(0, dtype=torch.float64, device=acc.device)
+    ext.triple_cg_dev(float(r2_old), acc, empty if clear is None else clear,
+                      p.data, norm_or_empty(p), Ap.data, norm_or_empty(Ap),
+                      x.data, norm_or_empty(x), r.data, norm_or_empty(r),
+                      p.volume_cb, p.n_parity * p.volume_cb, p.ncomp,
+                      empty if slots is None else slots, int(nslots),
+                      int(slot_stride))
+
+
 def xmy_norm2(x: SpinorField, y: SpinorField) -> float:
     """y = x - y; returns ||y||^2."""
     if on_gpu(x, y):

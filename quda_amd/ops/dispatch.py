@@ -144,21 +144,90 @@ def _autotune_on() -> bool:
     return _AUTOTUNE
 
 
+_TUNE_SCRATCH = {}
+
+
+def _tune_scratch(device, n: int) -> torch.Tensor:
+    """Accumulator for the autotuner's repeated fused-dot launches (a tuning
+    pass must never add into the caller's dot_result); private to the
+    tuning path and zeroed again after each pass."""
+    t = _TUNE_SCRATCH.get(str(device))
+    if t is None or t.numel() < n:
+        t = torch.zeros(n, dtype=torch.float64, device=device)
+        _TUNE_SCRATCH[str(device)] = t
+    return t
+
+
+def autotune_enabled() -> bool:
+    return _autotune_on()
+
+
+def set_autotune(v: bool) -> None:
+    """Switch the dispatch-level autotuner on or off (overrides
+    QUDA_AMD_AUTOTUNE)."""
+    global _AUTOTUNE
+    _AUTOTUNE = bool(v)
+
+
+def fused_epilogue_ok(*fields) -> bool:
+    """True where dslash_wilson takes out2= / dot_with=: always on the CPU
+    oracle; on the GPU for the single-kernel launches (local, or the
+    blocking ghost-aware kernel with the policy autotuner off) with the
+    LDS-tiled policy and the 64-thread occupancy experiment off. Elsewhere — the interior/exterior split defers
+    boundary epilogues to the exterior kernel, and the LDS-tiled kernel has
+    no fused epilogue — the operators issue the unfused launch sequence."""
+    if not on_gpu(*fields):
+        return True
+    import os
+    from ..parallel import comms
+    if hip_ext().get_dslash_lds() or hip_ext().get_dslash_waves():
+        return False
+    if not comms.comm_mask():
+        return True
+    return (os.environ.get("QUDA_AMD_BLOCKING_COMMS", "0") == "1"
+            and dslash_policy() == "fused")
+
+
 def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
                   parity: int, dagger: bool = False, mode: int = PLAIN,
                   a: float = 1.0, x: Optional[SpinorField] = None,
                   clover=None, clover_inverse: bool = False,
-                  twist=(0.0, 0.0)):
+                  twist=(0.0, 0.0), out2: Optional[SpinorField] = None,
+                  dot_with: Optional[SpinorField] = None,
+                  dot_result: Optional[torch.Tensor] = None,
+                  dot_slots: int = 1, dot_stride: int = 1):
     """Apply the fused Wilson(-clover/-twisted) stencil; out at `parity`,
     in at the opposite parity; x (same parity as out) enables the xpay
     term; twist=(b_re,b_im) feeds the TWIST_*/CLOVTW_* epilogues
-    (T(b) v = b_re v + i b_im g5 v)."""
+    (T(b) v = b_re v + i b_im g5 v).
+
+    Fused epilogues, where fused_epilogue_ok() (both act on `out` as
+    stored, i.e. after its precision's quantisation):
+      out2=      CLOV_POST, no dagger: out2 = A out, A the launch's clover
+      dot_with=  dagger PLAIN xpay: Re <dot_with, out> is added into
+                 dot_result (float64 tensor on the fields' device; the caller
+                 zeroes it), spread over the dot_slots words
+                 dot_result[s * dot_stride]: the dot is their sum
+    """
     from ..parallel import comms
     geo = out.geo
     xpay = x is not None
     mask = comms.comm_mask()
+    epi = ""
+    if out2 is not None:
+        assert dot_with is None and mode == CLOV_POST and not dagger, \
+            "out2: CLOV_POST without dagger only"
+        epi = "/out2"
+    if dot_with is not None:
+        assert dot_result is not None and mode == PLAIN and dagger and xpay, \
+            "dot_with: dagger PLAIN xpay only, with a dot_result tensor"
+        epi = "/dot"
+    if epi and not fused_epilogue_ok(out, inp):
+        raise RuntimeError("dslash_wilson: fused epilogue not available for "
+                           "this launch (check fused_epilogue_ok first)")
     trace_record("dslash_wilson",
-                 f"{geo.dims}/p{parity}/m{mode}/dag{int(dagger)}/{inp.precision}")
+                 f"{geo.dims}/p{parity}/m{mode}/dag{int(dagger)}/{inp.precision}"
+                 f"{epi}")
     if on_gpu(out, inp):
         ext = hip_ext()
         cl_t = torch.empty(0, dtype=out.data.dtype, device=out.device)
@@ -166,26 +235,49 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
             cl_t = clover.inv_data if clover_inverse else clover.data
         xf = x if x is not None else out
 
-        def launch(kt, ghosts=[], nrms=[], face_cb=[]):
+        def launch(kt, ghosts=[], nrms=[], face_cb=[], result=dot_result):
+            kw = {}
+            if out2 is not None:
+                kw = dict(out2=out2.data, out2_n=norm_or_empty(out2))
+            elif dot_with is not None:
+                kw = dict(dot_y=dot_with.data, dot_y_n=norm_or_empty(dot_with),
+                          dot_result=result, dot_slots=int(dot_slots),
+                          dot_stride=int(dot_stride))
             ext.dslash_wilson(
                 out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
                 gauge.data, cl_t, xf.data, norm_or_empty(xf),
                 list(geo.dims), geo.parity_offset, geo.volume_cb, parity,
                 bool(dagger), mode, xpay, float(a),
                 RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb,
-                mask if kt else 0, kt, float(twist[0]), float(twist[1]))
+                mask if kt else 0, kt, float(twist[0]), float(twist[1]), **kw)
 
         if not mask:
             # autotuned workgroup size (ref: lib/tune.cpp tuneLaunch —
             # first call per (kernel, dims, precision, mode) key measures
             # the candidates, later calls hit the cache; the dslash
-            # overwrites `out`, so re-running it during tuning is safe)
+            # overwrites `out`, so re-running it during tuning is safe —
+            # except the fused dot, which ADDS into its result: the tuning
+            # launches of that variant accumulate into a scratch tensor).
+            # The fused-epilogue kernels tune under keys of their own.
             if _autotune_on():
                 from ..utils.tune import tune_dslash
                 key = (f"dslash_wilson/{'x'.join(map(str, geo.dims))}/"
                        f"{inp.precision}/r{RECON_COMPS[gauge.reconstruct]}"
-                       f"/m{mode}/x{int(xpay)}")
-                tune_dslash(lambda: launch(0), key)
+                       f"/m{mode}/x{int(xpay)}{epi}")
+                if dot_with is not None:
+                    used = []
+
+                    def tune_launch():
+                        scratch = _tune_scratch(
+                            out.device, (dot_slots - 1) * dot_stride + 1)
+                        used.append(scratch)
+                        launch(0, result=scratch)
+
+                    tune_dslash(tune_launch, key)
+                    if used:
+                        used[-1].zero_()
+                else:
+                    tune_dslash(lambda: launch(0), key)
             launch(0)
             return out
         # comm-overlap policy (role of ref lib/dslash_policy.hpp): pack ->
@@ -271,6 +363,13 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     else:
         res = a * res
     out.from_complex(res.unsqueeze(0))
+    # fused epilogues from the existing reference ops, on `out` as stored
+    if out2 is not None:
+        A = clover.to_complex(inverse=clover_inverse)[parity]
+        out2.from_complex(ref.apply_clover(A, out.to_complex()[0]).unsqueeze(0))
+    if dot_with is not None:
+        from . import blas
+        dot_result[0] += blas.re_dot(dot_with, out)
     return out
 
 

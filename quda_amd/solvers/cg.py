@@ -48,6 +48,12 @@ def hq_residual(x: SpinorField, r: SpinorField) -> float:
     return sqrt(num / den)
 
 
+# device-side pAp accumulator of cg_solve: partial-sum words and their
+# spacing in float64 (16 = one 128-byte line each)
+_SLOTS = 32
+_STRIDE = 16
+
+
 def cg_solve(op, x: SpinorField, b: SpinorField, *,
              op_sloppy=None, sloppy: Optional[str] = None,
              tol: float = 1e-8, maxiter: int = 1000,
@@ -105,16 +111,51 @@ def cg_solve(op, x: SpinorField, b: SpinorField, *,
     maxr = sqrt(r2)    # max residual since last reliable update
     k = 0
     x_s_dirty = False  # x_s holds progress not yet folded into x
+    # Device-side pAp: where the sloppy operator can fold <p, Ap> into its
+    # last dslash (MdagM_dot), the dot, the division alpha = r2 / pAp and
+    # the residual norm all stay on the GPU and ONE 16-byte D2H read per
+    # iteration returns (pAp, ||r||^2). Two accumulators are used
+    # alternately: [pAp, r2, pad.., then _SLOTS partial-sum words, one per
+    # 128-byte line — thousands of atomics on a single word serialise]; the
+    # update kernel of iteration k sums the slots and zeroes the accumulator
+    # of iteration k+1, so re-zeroing costs no launch. A distributed pAp
+    # needs the host allreduce and the deterministic mode needs ordered
+    # partials: both keep the host path below.
+    from ..ops.dispatch import on_gpu
+    from ..parallel import comms
+    fused_dot = (hasattr(op_sloppy, "MdagM_dot") and on_gpu(p, Ap)
+                 and not comms.is_distributed()
+                 and not blas.deterministic_reductions())
+    if fused_dot:
+        import torch
+        n_acc = _STRIDE * (1 + _SLOTS)
+        acc = torch.zeros(2 * n_acc, dtype=torch.float64,
+                          device=p.data.device)
+        accs = (acc[:n_acc], acc[n_acc:])
+        heads = tuple(a[:2] for a in accs)
+        slots = tuple(a[_STRIDE:] for a in accs)
     while r2 > stop and k < maxiter:
-        op_sloppy.MdagM(Ap, p, tmp_s)
-        pAp = blas.re_dot(p, Ap)
-        if pAp <= 0.0:
-            break  # breakdown (ref: inv_cg_quda.cpp:265 checks)
-        alpha = r2 / pAp
-        x_s_dirty = True
-        r2_old = r2
-        # fused: x_s += alpha p; r_s -= alpha Ap; r2 = ||r_s||^2
-        r2 = blas.triple_cg_update(alpha, p, Ap, x_s, r_s)
+        if fused_dot:
+            cur = k & 1
+            op_sloppy.MdagM_dot(Ap, p, tmp_s, slots[cur], _SLOTS, _STRIDE)
+            blas.triple_cg_update_dev(r2, heads[cur], accs[1 - cur], p, Ap,
+                                      x_s, r_s, slots[cur], _SLOTS, _STRIDE)
+            pAp, r2_new = heads[cur].tolist()
+            if pAp <= 0.0:
+                break  # the kernel left x_s, r_s untouched
+            x_s_dirty = True
+            r2_old = r2
+            r2 = r2_new
+        else:
+            op_sloppy.MdagM(Ap, p, tmp_s)
+            pAp = blas.re_dot(p, Ap)
+            if pAp <= 0.0:
+                break  # breakdown (ref: inv_cg_quda.cpp:265 checks)
+            alpha = r2 / pAp
+            x_s_dirty = True
+            r2_old = r2
+            # fused: x_s += alpha p; r_s -= alpha Ap; r2 = ||r_s||^2
+            r2 = blas.triple_cg_update(alpha, p, Ap, x_s, r_s)
         k += 1
         rnorm = sqrt(r2)
         maxr = max(maxr, rnorm)

@@ -104,6 +104,14 @@ def get_tuner() -> Tuner:
     return _TUNER
 
 
+def set_tuner(tuner: Optional[Tuner]) -> Optional[Tuner]:
+    """Install `tuner` as the process tuner (None: a fresh default one is
+    built on next use); returns the one it replaces."""
+    global _TUNER
+    prev, _TUNER = _TUNER, tuner
+    return prev
+
+
 def tune_dslash(example_call: Callable[[], None], key: str) -> str:
     """Tune the dslash workgroup size for a representative launch
     (winner applied via the set_dslash_block binding)."""
