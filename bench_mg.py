@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--smooth-sweep", action="store_true",
                     help="after one MG setup, sweep (nu_post, coarse_tol) "
                          "V-cycle configs reusing the same null vectors")
+    ap.add_argument("--native-transfer", action="store_true",
+                    help="restrict/prolong/block-orthonormalize through the "
+                         "HIP kernels (MGParam.native_transfer=True)")
     args = ap.parse_args()
     dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     dims = tuple(int(x) for x in args.lattice.split(","))
@@ -91,7 +94,8 @@ def main():
                            n_vec=args.nvec, nu_post=4, coarse_tol=5e-2,
                            levels=args.levels, n_vec2=args.nvec2,
                            block2=(2, 2, 2, 2),
-                           null_tol=1e-4, null_maxiter=300))
+                           null_tol=1e-4, null_maxiter=300,
+                           native_transfer=args.native_transfer or None))
         sync()
         t_setup = time.perf_counter() - t0
 
@@ -137,10 +141,13 @@ def main():
             "metric": "mg_gcr_speedup",
             "lattice": "x".join(map(str, dims)), "kappa": kappa,
             "mg_setup_s": round(t_setup, 2),
+            "native_transfer": bool(mg.transfer.native_active),
             "plain_gcr": {"iters": st_plain.iters, "secs": round(t_plain, 2),
                           "converged": st_plain.converged},
             "mg_gcr": {"iters": st_mg.iters, "secs": round(t_mg, 2),
-                       "converged": st_mg.converged, "true_res": tr},
+                       "converged": st_mg.converged, "true_res": tr,
+                       "ms_per_iter": round(1e3 * t_mg / max(st_mg.iters, 1),
+                                            2)},
             "iter_reduction": round(st_plain.iters / max(st_mg.iters, 1), 1),
         }), flush=True)
 

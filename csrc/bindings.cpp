@@ -785,7 +785,113 @@ static void coarse_dslash_mfma(at::Tensor mats, at::Tensor nbr9,
   check_launch("coarse_dslash_mfma");
 }
 
+// Multigrid transfer (csrc/transfer.hip). Every shape the kernels index by
+// is checked here; the tables' entries are range-checked in the kernels.
+static TransferCall transfer_call(const char *what, const at::Tensor &field,
+                                  const at::Tensor &coarse,
+                                  const at::Tensor &Vn,
+                                  const at::Tensor &table, bool table_is_agg) {
+  TORCH_CHECK(field.is_cuda() && field.is_contiguous() && field.dim() == 4,
+              what, ": field must be a contiguous GPU spinor field");
+  const int prec = prec_of(field);
+  TORCH_CHECK(prec <= 1, what, ": double or single fields only");
+  const int W = chunk_w_of(field);
+  const long Vcb = field.size(2);
+  TORCH_CHECK(field.size(0) == 2 && field.size(1) * W == 24 &&
+                  field.size(3) == W && Vcb > 0,
+              what, ": field is not a full-parity nspin=4 field");
+  const auto ctype = prec == 0 ? at::kComplexDouble : at::kComplexFloat;
+  auto same_dev = [&](const at::Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == field.device() &&
+                    t.is_contiguous(),
+                what, ": ", name, " must be contiguous on the field's device");
+  };
+  same_dev(coarse, "coarse");
+  same_dev(Vn, "V");
+  same_dev(table, "table");
+  TORCH_CHECK(coarse.scalar_type() == ctype && Vn.scalar_type() == ctype, what,
+              ": coarse and V must be complex of the field's real type");
+  TORCH_CHECK(coarse.dim() == 3 && coarse.size(1) == 2, what,
+              ": coarse must be [Na, 2, Nv]");
+  const long Na = coarse.size(0), Nv = coarse.size(2);
+  TORCH_CHECK(table.scalar_type() == at::kInt, what, ": table must be int32");
+  TORCH_CHECK(Na > 0 && (2 * Vcb) % Na == 0, what,
+              ": Na does not divide the volume");
+  const long B = 2 * Vcb / Na;
+  if (table_is_agg) {  // prolong: site-fastest V
+    TORCH_CHECK(Vn.dim() == 4 && Vn.size(0) == 2 && Vn.size(1) == 6 &&
+                    Vn.size(2) == Nv && Vn.size(3) == 2 * Vcb,
+                what, ": Vn must be [2, 6, Nv, 2*Vcb]");
+    TORCH_CHECK(table.dim() == 1 && table.size(0) == 2 * Vcb, what,
+                ": agg_of_site must be [2*Vcb]");
+  } else {             // restrict: aggregate-ordered V
+    TORCH_CHECK(Vn.dim() == 5 && Vn.size(0) == Na && Vn.size(1) == B &&
+                    Vn.size(2) == 4 && Vn.size(3) == 3 && Vn.size(4) == Nv,
+                what, ": V must be [Na, B, 4, 3, Nv]");
+    TORCH_CHECK(table.dim() == 2 && table.size(0) == Na && table.size(1) == B,
+                what, ": site_tab must be [Na, B]");
+  }
+  TORCH_CHECK(Nv < (1L << 20) && B < (1L << 28), what, ": sizes out of range");
+  TransferCall c{};
+  c.field = BlasField{field.data_ptr(), nullptr, Vcb};
+  c.coarse = coarse.data_ptr();
+  c.Vn = table_is_agg ? Vn.data_ptr() : nullptr;
+  c.V = table_is_agg ? nullptr : Vn.data_ptr();
+  c.agg_of_site = table_is_agg ? table.data_ptr<int>() : nullptr;
+  c.site_tab = table_is_agg ? nullptr : table.data_ptr<int>();
+  c.Na = Na;
+  c.B = (int)B;
+  c.Nv = (int)Nv;
+  c.prec = prec;
+  TORCH_CHECK(qa_transfer_grid_ok(c), what, ": launch grid out of range");
+  return c;
+}
+
+static void transfer_prolong(at::Tensor out, at::Tensor coarse, at::Tensor Vn,
+                             at::Tensor agg_of_site) {
+  TransferCall c = transfer_call("transfer_prolong", out, coarse, Vn,
+                                 agg_of_site, true);
+  launch_transfer_prolong(c, stream());
+  check_launch("transfer_prolong");
+}
+
+static void transfer_restrict(at::Tensor coarse_out, at::Tensor in,
+                              at::Tensor V, at::Tensor site_tab) {
+  TransferCall c = transfer_call("transfer_restrict", in, coarse_out, V,
+                                 site_tab, false);
+  launch_transfer_restrict(c, stream());
+  check_launch("transfer_restrict");
+}
+
+static void transfer_block_ortho(at::Tensor V, int64_t passes) {
+  TORCH_CHECK(V.is_cuda() && V.is_contiguous() &&
+                  V.scalar_type() == at::kComplexDouble,
+              "transfer_block_ortho: V must be a contiguous complex128 GPU "
+              "tensor");
+  TORCH_CHECK(V.dim() == 5 && V.size(2) == 4 && V.size(3) == 3,
+              "transfer_block_ortho: V must be [Na, B, 4, 3, Nv]");
+  TORCH_CHECK(passes >= 0 && passes <= 16, "transfer_block_ortho: passes");
+  const long Na = V.size(0), B = V.size(1), Nv = V.size(4);
+  TORCH_CHECK(Na > 0 && B > 0 && Nv > 0 && 2 * Na < (1L << 31) - 1 &&
+                  6 * B < (1L << 31) - 1 && Nv < (1L << 20),
+              "transfer_block_ortho: sizes out of range");
+  BlockOrthoCall c{V.data_ptr(), Na, (int)B, (int)Nv, (int)passes};
+  launch_transfer_block_ortho(c, stream());
+  check_launch("transfer_block_ortho");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("transfer_prolong", &transfer_prolong,
+        "MG prolongator: fine field = V * coarse, written in native storage",
+        py::arg("out"), py::arg("coarse"), py::arg("Vn"),
+        py::arg("agg_of_site"));
+  m.def("transfer_restrict", &transfer_restrict,
+        "MG restrictor: coarse = V^dag * fine field (fixed-order reduction)",
+        py::arg("coarse_out"), py::arg("in"), py::arg("V"),
+        py::arg("site_tab"));
+  m.def("transfer_block_ortho", &transfer_block_ortho,
+        "in-place per-(aggregate, chirality) modified Gram-Schmidt of V",
+        py::arg("V"), py::arg("passes") = 2);
   m.def("dslash_wilson", &dslash_wilson, "Wilson(-clover/-twisted) dslash",
         py::arg("out"), py::arg("out_n"), py::arg("in"), py::arg("in_n"),
         py::arg("gauge"), py::arg("clover"), py::arg("x"), py::arg("x_n"),

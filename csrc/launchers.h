@@ -360,3 +360,30 @@ struct Eofa5Call {
   int kind;  // 0 = m5_eofa, 1 = m5inv_eofa
 };
 void launch_eofa5(const Eofa5Call &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
+// multigrid transfer, fine Wilson level (csrc/transfer.hip). Double/single.
+struct TransferCall {
+  BlasField field;         // full-parity fine field (Vcb = cb volume)
+  void *coarse;            // [Na][2][Nv] complex of the field's real type
+  const void *Vn;          // [2][6][Nv][2*Vcb] complex, site-fastest (prolong)
+  const void *V;           // [Na][B][4][3][Nv] complex (restrict)
+  const int *agg_of_site;  // [2*Vcb] aggregate of each fine site (prolong)
+  const int *site_tab;     // [Na][B] fine site of each (a, b) (restrict)
+  long Na;
+  int B;
+  int Nv;
+  int prec;                // 0 double, 1 single
+};
+bool qa_transfer_grid_ok(const TransferCall &c);
+void launch_transfer_prolong(const TransferCall &c, hipStream_t st);
+void launch_transfer_restrict(const TransferCall &c, hipStream_t st);
+
+struct BlockOrthoCall {
+  void *V;  // [Na][B][4][3][Nv] complex double, orthonormalized in place
+  long Na;
+  int B;
+  int Nv;
+  int passes;
+};
+void launch_transfer_block_ortho(const BlockOrthoCall &c, hipStream_t st);

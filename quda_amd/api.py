@@ -547,7 +547,10 @@ def eigensolve_quda(p: InvertParam, e: EigParam):
 def new_multigrid_quda(p: InvertParam, block=(2, 2, 2, 2), n_vec: int = 4,
                        **kw):
     """ref: newMultigridQuda interface_quda.cpp:2772. Returns an MG object
-    whose .precond plugs into InvertParam.preconditioner."""
+    whose .precond plugs into InvertParam.preconditioner. Further MGParam
+    fields pass through **kw, e.g. native_transfer=True to run restrict,
+    prolong and the block-orthonormalization through the HIP transfer
+    kernels (default None: env QUDA_AMD_MG_NATIVE_TRANSFER, off)."""
     from .mg import MG, MGParam
     d = _make_dirac(InvertParam(**{**p.__dict__,
                                    "solution_type": SolutionType.MAT}))

@@ -34,6 +34,9 @@ class MGParam:
     null_tol: float = 5e-5
     null_maxiter: int = 200
     seed: int = 500
+    # HIP restrict/prolong/block-orthonormalize (csrc/transfer.hip) instead
+    # of the torch transfer; None = env QUDA_AMD_MG_NATIVE_TRANSFER (off)
+    native_transfer: Optional[bool] = None
 
 
 class MG:
@@ -49,7 +52,8 @@ class MG:
                 op, param.n_vec, tol=param.null_tol,
                 maxiter=param.null_maxiter, seed=param.seed)
         self.null_vectors = vectors
-        self.transfer = Transfer(op.geo, param.block, vectors)
+        self.transfer = Transfer(op.geo, param.block, vectors,
+                                 native=param.native_transfer)
         self.coarse = build_coarse_op(op, self.transfer)
         self.coarse_mg = None
         if param.levels >= 3:

@@ -1035,3 +1035,43 @@ def dslash_wilson_slice(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     oc[0][sl] = res
     out.from_complex(oc)
     return out
+
+
+# ---------------------------------------------------------------------------
+# multigrid transfer (csrc/transfer.hip). These three are GPU-only entry
+# points: mg/transfer.py decides eligibility and keeps the torch path for
+# everything else, so reaching them without the extension is an error.
+# ---------------------------------------------------------------------------
+def transfer_prolong(out: SpinorField, coarse: torch.Tensor,
+                     Vn: torch.Tensor, agg_of_site: torch.Tensor):
+    """out(g,s,c) = sum_v V(g,s,c,v) coarse[agg(g), chi(s), v] written
+    straight into out's native storage; coarse/Vn complex of out's real
+    type."""
+    assert on_gpu(out), "transfer_prolong: native kernel needs a GPU field"
+    trace_record("transfer_prolong",
+                 f"{out.geo.dims}/nv{Vn.shape[2]}/{out.precision}")
+    hip_ext().transfer_prolong(out.data, coarse, Vn, agg_of_site)
+    return out
+
+
+def transfer_restrict(inp: SpinorField, V: torch.Tensor,
+                      site_tab: torch.Tensor) -> torch.Tensor:
+    """[Na, 2, Nv] = V^dag inp from the aggregate-ordered V [Na,B,4,3,Nv]
+    (complex of inp's real type, as is the result), reduced in a fixed
+    order: bitwise reproducible."""
+    assert on_gpu(inp), "transfer_restrict: native kernel needs a GPU field"
+    trace_record("transfer_restrict",
+                 f"{inp.geo.dims}/nv{V.shape[-1]}/{inp.precision}")
+    out = torch.empty((site_tab.shape[0], 2, V.shape[-1]), dtype=V.dtype,
+                      device=inp.device)
+    hip_ext().transfer_restrict(out, inp.data, V, site_tab)
+    return out
+
+
+def transfer_block_ortho(V: torch.Tensor, passes: int = 2) -> torch.Tensor:
+    """In-place per-(aggregate, chirality) modified Gram-Schmidt of the
+    contiguous complex128 GPU tensor V [Na, B, 4, 3, Nv]."""
+    assert V.device.type == "cuda", "transfer_block_ortho: GPU tensor only"
+    trace_record("transfer_block_ortho", f"{tuple(V.shape)}/p{passes}")
+    hip_ext().transfer_block_ortho(V, int(passes))
+    return V

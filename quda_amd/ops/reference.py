@@ -492,3 +492,31 @@ def m5inv_eofa(psi5, Ls, alpha, beta, mf, sh, pm, u, w, dagger=False):
                             device=psi5.device)
         out[:, :, sl, :] = torch.einsum("st,tvxc->svxc", Ainv, v[:, :, sl, :])
     return out.reshape(Ls * V, 4, 3)
+
+
+# ---------------------------------------------------------------------------
+# multigrid transfer, emulating csrc/transfer.hip index for index: the same
+# tables (mg/transfer.py transfer_tables) and the same V copies the kernels
+# read (prolong: the site-fastest Vn of pack_vn; restrict: the aggregate-
+# ordered V), so the table construction is testable on CPU
+# ---------------------------------------------------------------------------
+def prolong_from_tables(coarse: torch.Tensor, Vn: torch.Tensor,
+                        agg_of_site: torch.Tensor) -> torch.Tensor:
+    """coarse [Na,2,Nv], Vn [2,6,Nv,G], agg_of_site [G] -> fine field in
+    the oracle layout [2, G/2, 4, 3]: out(g,s,c) = sum_v V(g,s,c,v) *
+    coarse[agg(g), chi(s), v], with g = parity*Vcb + x."""
+    G = Vn.shape[-1]
+    cg = coarse.to(Vn.dtype)[agg_of_site.long()]          # [G, 2, Nv]
+    out = torch.einsum("xkvg,gxv->gxk", Vn, cg)           # [G, 2, 6]
+    return out.reshape(2, G // 2, 4, 3)
+
+
+def restrict_from_tables(psi: torch.Tensor, V: torch.Tensor,
+                         site_tab: torch.Tensor) -> torch.Tensor:
+    """psi [2, Vcb, 4, 3], aggregate-ordered V [Na,B,4,3,Nv], site_tab
+    [Na,B] -> [Na,2,Nv]: c[a,chi,v] = sum_{b,k} conj(V[a,b,chi,k,v])
+    psi(g,chi,k) with g = site_tab[a,b]."""
+    Na, B, _, _, Nv = V.shape
+    pg = psi.to(V.dtype).reshape(-1, 2, 6)[site_tab.long()]   # [Na, B, 2, 6]
+    return torch.einsum("abxkv,abxk->axv",
+                        V.reshape(Na, B, 2, 6, Nv).conj(), pg)
