@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from quda_amd import GaugeField, LatticeGeometry, SpinorField  # noqa: E402
 from quda_amd.fields.clover import CloverField  # noqa: E402
-from quda_amd.mg import MG, MGParam  # noqa: E402
+from quda_amd.mg import MG, MGParam, build_coarse_op  # noqa: E402
 from quda_amd.models import DiracClover  # noqa: E402
 from quda_amd.ops import blas  # noqa: E402
 from quda_amd.ops import reference as ref  # noqa: E402
@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--native-transfer", action="store_true",
                     help="restrict/prolong/block-orthonormalize through the "
                          "HIP kernels (MGParam.native_transfer=True)")
+    ap.add_argument("--native-galerkin", action="store_true",
+                    help="build the coarse operator in the HIP Galerkin "
+                         "kernel (MGParam.native_galerkin=True)")
     args = ap.parse_args()
     dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     dims = tuple(int(x) for x in args.lattice.split(","))
@@ -95,9 +98,16 @@ def main():
                            levels=args.levels, n_vec2=args.nvec2,
                            block2=(2, 2, 2, 2),
                            null_tol=1e-4, null_maxiter=300,
-                           native_transfer=args.native_transfer or None))
+                           native_transfer=args.native_transfer or None,
+                           native_galerkin=args.native_galerkin or None))
         sync()
         t_setup = time.perf_counter() - t0
+        # the coarse-operator build alone, once more on the finished setup
+        sync()
+        t0 = time.perf_counter()
+        build_coarse_op(d, mg.transfer, native=args.native_galerkin or None)
+        sync()
+        t_coarse = time.perf_counter() - t0
 
         x0 = SpinorField(geo, "double", dev)
         t0 = time.perf_counter()
@@ -142,6 +152,8 @@ def main():
             "lattice": "x".join(map(str, dims)), "kappa": kappa,
             "mg_setup_s": round(t_setup, 2),
             "native_transfer": bool(mg.transfer.native_active),
+            "native_galerkin": bool(mg.coarse_native),
+            "coarse_build_s": round(t_coarse, 4),
             "plain_gcr": {"iters": st_plain.iters, "secs": round(t_plain, 2),
                           "converged": st_plain.converged},
             "mg_gcr": {"iters": st_mg.iters, "secs": round(t_mg, 2),

@@ -36,6 +36,7 @@ KERNEL_SOURCES = [
     "coarse.hip",
     "heatbath.hip",
     "transfer.hip",
+    "galerkin.hip",
 ]
 BINDING_SOURCES = ["bindings.cpp"]
 

@@ -880,7 +880,86 @@ static void transfer_block_ortho(at::Tensor V, int64_t passes) {
   check_launch("transfer_block_ortho");
 }
 
+// Galerkin coarse-operator build (csrc/galerkin.hip): X, Y and the scratch are
+// written in full. Shapes are checked here; the neighbour table's entries are
+// range-checked in the kernel.
+static void galerkin_build(at::Tensor X, at::Tensor Y, at::Tensor scratch,
+                           at::Tensor V, at::Tensor nbr, at::Tensor bnd,
+                           at::Tensor link, c10::optional<at::Tensor> clov,
+                           at::Tensor coef) {
+  const char *what = "galerkin_build";
+  TORCH_CHECK(V.is_cuda() && V.is_contiguous() &&
+                  V.scalar_type() == at::kComplexDouble,
+              what, ": V must be a contiguous complex128 GPU tensor");
+  TORCH_CHECK(V.dim() == 5 && V.size(2) == 4 && V.size(3) == 3, what,
+              ": V must be [Na, B, 4, 3, Nv]");
+  const long Na = V.size(0), B = V.size(1), Nv = V.size(4);
+  TORCH_CHECK(Na > 0 && B > 0 && Nv > 0 && Nv < (1L << 20) && B < (1L << 28) &&
+                  Na * B < (1L << 31) - 1,
+              what, ": sizes out of range");
+  const long rows = Na * B, Nc = 2 * Nv;
+  auto same_dev = [&](const at::Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == V.device() && t.is_contiguous(),
+                what, ": ", name, " must be contiguous on V's device");
+  };
+  auto c128 = [&](const at::Tensor &t, const char *name) {
+    same_dev(t, name);
+    TORCH_CHECK(t.scalar_type() == at::kComplexDouble, what, ": ", name,
+                " must be complex128");
+  };
+  c128(X, "X");
+  c128(Y, "Y");
+  c128(scratch, "scratch");
+  c128(link, "link");
+  c128(coef, "coef");
+  TORCH_CHECK(X.dim() == 3 && X.size(0) == Na && X.size(1) == Nc &&
+                  X.size(2) == Nc,
+              what, ": X must be [Na, 2*Nv, 2*Nv]");
+  TORCH_CHECK(Y.dim() == 4 && Y.size(0) == 8 && Y.size(1) == Na &&
+                  Y.size(2) == Nc && Y.size(3) == Nc,
+              what, ": Y must be [8, Na, 2*Nv, 2*Nv]");
+  TORCH_CHECK(scratch.dim() == 4 && scratch.size(0) == 9 &&
+                  scratch.size(1) == Na && scratch.size(2) == Nc &&
+                  scratch.size(3) == Nc,
+              what, ": scratch must be [9, Na, 2*Nv, 2*Nv]");
+  same_dev(nbr, "nbr");
+  same_dev(bnd, "bnd");
+  TORCH_CHECK(nbr.scalar_type() == at::kInt && nbr.dim() == 2 &&
+                  nbr.size(0) == rows && nbr.size(1) == 8,
+              what, ": nbr must be int32 [Na*B, 8]");
+  TORCH_CHECK(bnd.scalar_type() == at::kByte && bnd.dim() == 1 &&
+                  bnd.size(0) == rows,
+              what, ": bnd must be uint8 [Na*B]");
+  TORCH_CHECK(link.dim() == 4 && link.size(0) == rows && link.size(1) == 8 &&
+                  link.size(2) == 3 && link.size(3) == 3,
+              what, ": link must be [Na*B, 8, 3, 3]");
+  TORCH_CHECK(coef.dim() == 3 && coef.size(0) == 8 && coef.size(1) == 4 &&
+                  coef.size(2) == 4,
+              what, ": coef must be [8, 4, 4]");
+  const void *cl = nullptr;
+  if (clov.has_value()) {
+    c128(*clov, "clov");
+    TORCH_CHECK(clov->dim() == 3 && clov->size(0) == rows &&
+                    clov->size(1) == 12 && clov->size(2) == 12,
+                what, ": clov must be [Na*B, 12, 12]");
+    cl = clov->data_ptr();
+  }
+  GalerkinCall c{X.data_ptr(), Y.data_ptr(), scratch.data_ptr(),
+                 V.data_ptr(), nbr.data_ptr<int>(),
+                 bnd.data_ptr<unsigned char>(), link.data_ptr(), cl,
+                 coef.data_ptr(), Na, (int)B, (int)Nv};
+  TORCH_CHECK(qa_galerkin_grid_ok(c), what, ": launch grid out of range");
+  launch_galerkin_build(c, stream());
+  check_launch(what);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("galerkin_build", &galerkin_build,
+        "Galerkin coarse operator X, Y[8] from the aggregate-ordered V "
+        "(fixed summation order)",
+        py::arg("X"), py::arg("Y"), py::arg("scratch"), py::arg("V"),
+        py::arg("nbr"), py::arg("bnd"), py::arg("link"), py::arg("clov"),
+        py::arg("coef"));
   m.def("transfer_prolong", &transfer_prolong,
         "MG prolongator: fine field = V * coarse, written in native storage",
         py::arg("out"), py::arg("coarse"), py::arg("Vn"),

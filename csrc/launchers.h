@@ -387,3 +387,22 @@ struct BlockOrthoCall {
   int passes;
 };
 void launch_transfer_block_ortho(const BlockOrthoCall &c, hipStream_t st);
+
+// Galerkin coarse-operator build, fine Wilson(-clover) level
+// (csrc/galerkin.hip). Complex double throughout; rows ab = a*B + b.
+struct GalerkinCall {
+  void *X;              // [Na][Nc][Nc], Nc = 2*Nv
+  void *Y;              // [8][Na][Nc][Nc]
+  void *scratch;        // [9][Na][Nc][Nc] interior part of each term
+  const void *V;        // [Na][B][12][Nv]
+  const int *nbr;       // [Na*B][8] row of the d-neighbour
+  const unsigned char *bnd;  // [Na*B] bit d: site on the d-face of its block
+  const void *link;     // [Na*B][8][3][3]
+  const void *clov;     // [Na*B][12][12] or null (identity)
+  const void *coef;     // [8][4][4] -kappa * P_d
+  long Na;
+  int B;
+  int Nv;
+};
+bool qa_galerkin_grid_ok(const GalerkinCall &c);
+void launch_galerkin_build(const GalerkinCall &c, hipStream_t st);

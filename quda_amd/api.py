@@ -550,7 +550,10 @@ def new_multigrid_quda(p: InvertParam, block=(2, 2, 2, 2), n_vec: int = 4,
     whose .precond plugs into InvertParam.preconditioner. Further MGParam
     fields pass through **kw, e.g. native_transfer=True to run restrict,
     prolong and the block-orthonormalization through the HIP transfer
-    kernels (default None: env QUDA_AMD_MG_NATIVE_TRANSFER, off)."""
+    kernels (default None: env QUDA_AMD_MG_NATIVE_TRANSFER, off), or
+    native_galerkin=True to build the coarse operator in the HIP Galerkin
+    kernel (default None: env QUDA_AMD_MG_NATIVE_GALERKIN, off). The two are
+    independent; mg.coarse_native tells which path built the operator."""
     from .mg import MG, MGParam
     d = _make_dirac(InvertParam(**{**p.__dict__,
                                    "solution_type": SolutionType.MAT}))

@@ -116,6 +116,8 @@ class CoarseOp:
     dirac_coarse.cpp), and the dagger runs in GATHER form using the
     neighbor rank's Y faces (exchanged once at construction)."""
 
+    native = False  # True: X and Y came from the HIP Galerkin kernel
+
     def __init__(self, X: torch.Tensor, Y: List[torch.Tensor], cd,
                  mask: int = 0):
         self.X = X
@@ -253,14 +255,27 @@ class CoarseOp:
         return A
 
 
-def build_coarse_op(op, transfer: Transfer) -> CoarseOp:
+def build_coarse_op(op, transfer: Transfer,
+                    native: Optional[bool] = None) -> CoarseOp:
     """Galerkin coarse operator of the FULL fine operator `op` (must expose
     M on full-parity SpinorFields and its piecewise structure via
     kappa/clover attributes): direction-separated triple products.
 
     The fine op is assumed of the form  M = Diag - kappa * sum_hops
-    (Wilson: Diag = 1; clover: Diag = A)."""
+    (Wilson: Diag = 1; clover: Diag = A).
+
+    native=True (or QUDA_AMD_MG_NATIVE_GALERKIN=1 when native is None)
+    computes X and Y in the HIP kernel of csrc/galerkin.hip where
+    mg.galerkin.galerkin_eligible allows it — complex128 V on the GPU,
+    single rank — and leaves every other input on the torch loop below.
+    The result's `native` attribute tells which one ran."""
     from ..parallel import comms
+    from .galerkin import build_coarse_native, galerkin_eligible
+    if galerkin_eligible(op, transfer, native):
+        X, Y = build_coarse_native(op, transfer)
+        cop = CoarseOp(X, Y, transfer.coarse_dims, mask=0)
+        cop.native = True
+        return cop
     geo = transfer.geo
     dev = transfer.device
     u_cb = op.gauge.to_complex()

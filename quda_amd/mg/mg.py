@@ -37,6 +37,10 @@ class MGParam:
     # HIP restrict/prolong/block-orthonormalize (csrc/transfer.hip) instead
     # of the torch transfer; None = env QUDA_AMD_MG_NATIVE_TRANSFER (off)
     native_transfer: Optional[bool] = None
+    # HIP Galerkin build of the coarse operator (csrc/galerkin.hip) instead
+    # of the torch column loop; None = env QUDA_AMD_MG_NATIVE_GALERKIN (off).
+    # Independent of native_transfer: either transfer feeds either build.
+    native_galerkin: Optional[bool] = None
 
 
 class MG:
@@ -54,7 +58,10 @@ class MG:
         self.null_vectors = vectors
         self.transfer = Transfer(op.geo, param.block, vectors,
                                  native=param.native_transfer)
-        self.coarse = build_coarse_op(op, self.transfer)
+        self.coarse = build_coarse_op(op, self.transfer,
+                                      native=param.native_galerkin)
+        # which path built X and Y (True: the HIP kernel)
+        self.coarse_native = bool(self.coarse.native)
         self.coarse_mg = None
         if param.levels >= 3:
             from .coarse_level import CoarseMG

@@ -1075,3 +1075,32 @@ def transfer_block_ortho(V: torch.Tensor, passes: int = 2) -> torch.Tensor:
     trace_record("transfer_block_ortho", f"{tuple(V.shape)}/p{passes}")
     hip_ext().transfer_block_ortho(V, int(passes))
     return V
+
+
+# ---------------------------------------------------------------------------
+# Galerkin coarse-operator build (csrc/galerkin.hip). GPU-only like the
+# transfer entries: mg/galerkin.py decides eligibility and coarse.py keeps
+# the torch build for everything else.
+# ---------------------------------------------------------------------------
+def galerkin_build(V: torch.Tensor, nbr_ab: torch.Tensor, bnd: torch.Tensor,
+                   link_ab: torch.Tensor, clov_ab: Optional[torch.Tensor],
+                   coef: torch.Tensor, X: Optional[torch.Tensor] = None,
+                   Y: Optional[torch.Tensor] = None):
+    """X [Na,Nc,Nc] and Y [8,Na,Nc,Nc] (complex128, Nc = 2*Nv) of the fine
+    Wilson(-clover) operator from the aggregate-ordered V [Na,B,4,3,Nv] and
+    the operands of mg.galerkin (nbr_ab, bnd, link_ab, clov_ab or None,
+    coef = -kappa P_d). Every entry of X and Y is written; the sums run in
+    a fixed order, so two builds agree bitwise. X / Y may be passed in."""
+    assert V.device.type == "cuda", "galerkin_build: GPU tensor only"
+    Na, B, _, _, Nv = V.shape
+    Nc = 2 * Nv
+    trace_record("galerkin_build",
+                 f"na{Na}/b{B}/nv{Nv}/{'clover' if clov_ab is not None else 'wilson'}")
+    if X is None:
+        X = torch.empty((Na, Nc, Nc), dtype=V.dtype, device=V.device)
+    if Y is None:
+        Y = torch.empty((8, Na, Nc, Nc), dtype=V.dtype, device=V.device)
+    scratch = torch.empty((9, Na, Nc, Nc), dtype=V.dtype, device=V.device)
+    hip_ext().galerkin_build(X, Y, scratch, V, nbr_ab, bnd, link_ab, clov_ab,
+                             coef)
+    return X, Y

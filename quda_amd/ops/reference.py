@@ -520,3 +520,54 @@ def restrict_from_tables(psi: torch.Tensor, V: torch.Tensor,
     pg = psi.to(V.dtype).reshape(-1, 2, 6)[site_tab.long()]   # [Na, B, 2, 6]
     return torch.einsum("abxkv,abxk->axv",
                         V.reshape(Na, B, 2, 6, Nv).conj(), pg)
+
+
+# ---------------------------------------------------------------------------
+# Galerkin coarse-operator build, emulating csrc/galerkin.hip on exactly its
+# operands (mg/galerkin.py galerkin_tables / galerkin_operands), batched over
+# all coarse columns: the CPU oracle of the kernel's index logic
+# ---------------------------------------------------------------------------
+def galerkin_from_tables(V: torch.Tensor, nbr_ab: torch.Tensor,
+                         bnd: torch.Tensor, link_ab: torch.Tensor,
+                         clov_ab, kappa):
+    """Aggregate-ordered V [Na,B,4,3,Nv], nbr_ab [Na*B,8], bnd [Na*B] (bit
+    d: the site is on the d-face of its block), link_ab [Na*B,8,3,3] (bwd
+    links daggered and shifted), clov_ab [Na*B,12,12] or None -> (X, [Y[d]])
+    with X, Y[d] [Na,Nc,Nc], Nc = 2*Nv, coarse index chi*Nv + v:
+
+      W_d(x; s,c,(chi',v)) = -kappa sum_{s' in chi'} P_d[s,s']
+                              sum_c' L_d(x)[c,c'] V(nbr_d(x); s',c',v)
+      M_d[a; (chi,w),(chi',v)] = sum_{x in a, s in chi, c} conj(V(x;s,c,w)) W_d
+
+    goes to Y[d] from the sites whose bnd bit d is set and to X from the
+    others; X also takes sum_x V^dag D V (D = 1, or the dense clov_ab)."""
+    Na, B, _, _, Nv = V.shape
+    G, Nc = Na * B, 2 * Nv
+    P = _gamma_tensors(V.device, V.dtype)
+    Vf = V.reshape(G, 2, 6, Nv)
+    Vc = V.reshape(Na, B, 2, 6, Nv).conj()
+
+    def contract(W):  # [G, 2, 6, 2, Nv] -> [Na, Nc, Nc]
+        return torch.einsum("abxkw,abxkyv->axwyv", Vc,
+                            W.reshape(Na, B, 2, 6, 2, Nv)).reshape(Na, Nc, Nc)
+
+    if clov_ab is not None:
+        W = torch.einsum("gkyl,gylv->gkyv", clov_ab.reshape(G, 12, 2, 6), Vf)
+    else:
+        W = torch.zeros((G, 2, 6, 2, Nv), dtype=V.dtype, device=V.device)
+        W[:, 0, :, 0] = Vf[:, 0]
+        W[:, 1, :, 1] = Vf[:, 1]
+    X = contract(W)
+    Y = []
+    for d in range(8):
+        mu, fwd = d // 2, d % 2
+        Vn = V.reshape(G, 4, 3, Nv)[nbr_ab[:, d].long()]
+        T = torch.einsum("gij,gsjv->gsiv", link_ab[:, d], Vn)
+        W = -kappa * torch.einsum("syt,gytcv->gscyv",
+                                  P[mu, 1 - fwd].reshape(4, 2, 2),
+                                  T.reshape(G, 2, 2, 3, Nv))
+        face = (((bnd.long() >> d) & 1) == 1).reshape(G, 1, 1, 1, 1)
+        zero = torch.zeros_like(W)
+        X = X + contract(torch.where(face, zero, W))
+        Y.append(contract(torch.where(face, W, zero)))
+    return X, Y
