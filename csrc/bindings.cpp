@@ -1011,7 +1011,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dslash_staggered", &dslash_staggered, "naive staggered dslash");
   m.def("set_dslash_block", &set_dslash_block, "autotuner: dslash workgroup size");
   m.def("set_dslash_waves", &set_dslash_waves,
-        "occupancy experiment: 0 default, 3 = 64-thread/3-wave variant");
+        "occupancy experiment: 0 default, 3 = 64-thread/3-wave variant "
+        "(half/single/quarter; double keeps its default kernel)");
   m.def("set_dslash_lds", &set_dslash_lds,
         "LDS-tiled dslash policy: 1 = stage the in-spinor halo tile in LDS "
         "(half/quarter, local, tile-divisible dims)");

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(DwfFusedTile<Prec>::MAX_THREADS) void k_dwf_fused(
     long jm[4];
 
     // gather + project all 8 neighbors first, then the gauge multiplies
-    // (the load-ILP shape of k_dslash_wilson, LBW == 0)
+    // (the load-ILP shape of k_dslash_wilson, ROUNDS == 1)
 #define QA_GATHER(MU)                                                     \
   {                                                                       \
     long j = neighbor_cb(xc, MU, +1, d);                                  \

@@ -104,6 +104,22 @@ __device__ __forceinline__ void clover_mul(cplx<R> out[4][3], const R diag[2][6]
   }
 }
 
+// Gather rounds of the body (dslash_wilson_body.inl pins them with a fence
+// that carries the accumulator):
+//   half/single/quarter, LBW = 0 : 1 — all 8 gathers in flight, then all
+//       multiplies. Fenced 2- and 4-round forms at 3-4 waves/SIMD were
+//       measured and did not beat it (profiles/r07_dslash_rounds.md).
+//   half/single/quarter, LBW > 0 : 2 rounds of 4 neighbors, so the cap is
+//       met without spilling
+//   double : 4 rounds of 2 neighbors. With 8 gathers in flight a double
+//       site does not fit the 512 registers of a lane (~750 B/lane of
+//       scratch, 1 wave/SIMD); 4 rounds need ~220 VGPRs -> 2 waves/SIMD.
+template <typename Prec, int LBW>
+constexpr int qa_dslash_rounds() {
+  if (sizeof(typename Prec::Real) == 8) return 4;
+  return LBW ? 2 : 1;
+}
+
 // LBW = 0: 256-thread cap, allocator unconstrained (measured 222 VGPRs ->
 // 2 waves/SIMD). LBW > 0: 64-thread workgroups with a minimum of LBW waves
 // per SIMD — caps the register allocation (512/LBW) to raise occupancy on
@@ -125,6 +141,7 @@ __global__ __launch_bounds__(LBW ? 64 : 256, LBW ? LBW : 1) void k_dslash_wilson
     SpinorAcc<Prec> x, GhostAcc<Prec> gh, typename Prec::Real br,
     typename Prec::Real bi) {
   using R = typename Prec::Real;
+  constexpr int ROUNDS = qa_dslash_rounds<Prec, LBW>();
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.Vcb) return;
 #include "dslash_wilson_body.inl"
@@ -135,9 +152,8 @@ __global__ __launch_bounds__(LBW ? 64 : 256, LBW ? LBW : 1) void k_dslash_wilson
 // round trip of out (kt 0/1 only: boundary sites of the interior kernel
 // defer their epilogue to the exterior kernel). Like the dot kernel below it
 // exists in the default 256-thread-cap form only: under the 64-thread
-// occupancy experiment (QUDA_AMD_DSLASH_WAVES=3, which spills) the
-// operators keep the unfused launch sequence. `out` is bitwise what
-// k_dslash_wilson stores.
+// occupancy experiment (QUDA_AMD_DSLASH_WAVES=3) the operators keep the
+// unfused launch sequence. `out` is bitwise what k_dslash_wilson stores.
 template <typename Prec, int RECON, bool DAG, bool XPAY, int KT = KT_LOCAL>
 __global__ __launch_bounds__(256, 1) void k_dslash_wilson_clov_out2(
     SpinorAcc<Prec> out, SpinorAcc<Prec> in, GaugeAcc<Prec, RECON> g,
@@ -146,7 +162,7 @@ __global__ __launch_bounds__(256, 1) void k_dslash_wilson_clov_out2(
   using R = typename Prec::Real;
   static_assert(KT == KT_LOCAL || KT == KT_FUSED);
   constexpr int MODE = CLOV_POST;
-  constexpr int LBW = 0;
+  constexpr int ROUNDS = qa_dslash_rounds<Prec, 0>();
   const R br = (R)0, bi = (R)0;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.Vcb) return;
@@ -188,7 +204,7 @@ __global__ __launch_bounds__(256, 1) void k_dslash_wilson_xpay_dot(
   static_assert(KT == KT_LOCAL || KT == KT_FUSED);
   constexpr int MODE = PLAIN;
   constexpr bool XPAY = true;
-  constexpr int LBW = 0;
+  constexpr int ROUNDS = qa_dslash_rounds<Prec, 0>();
   const R br = (R)0, bi = (R)0;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   double dot = 0.0;

@@ -3,8 +3,9 @@
 // compile the very same stencil. (A shared __device__ function was measured
 // to change the register allocation of the existing kernels: 206 VGPRs /
 // 2 waves per SIMD became 256 + AGPR copies / 1 wave.)
-// In scope at the include: Prec, RECON, DAG, MODE, XPAY, KT, LBW, R, the
-// kernel arguments out, in, g, clov, d, parity, a, x, gh, br, bi and the
+// In scope at the include: Prec, RECON, DAG, MODE, XPAY, KT, ROUNDS (gather
+// rounds of the stencil: 1, 2 or 4, see qa_dslash_rounds), R, the kernel
+// arguments out, in, g, clov, d, parity, a, x, gh, br, bi and the
 // site index i < d.Vcb. Leaves the finished site in acc[4][3] (not yet
 // stored). A kernel that needs the CLOV_POST site matrix afterwards declares
 // diag / tri itself and defines QA_DSLASH_CLOVER_DECLARED around the include.
@@ -93,33 +94,67 @@
     }                                                                     \
   }
 
-  if constexpr (LBW == 0) {
+  // Round fence. A round is "gather some directions, multiply them into
+  // acc"; the fence between two rounds keeps the next round's loads from
+  // being issued (and their destinations from being live) before this
+  // round's half-spinors and links are dead. It emits no instruction: acc
+  // is an in/out operand, so every multiply-add that feeds acc must finish
+  // above the fence, and the memory clobber keeps the later loads below it.
+  // __builtin_amdgcn_sched_barrier(0) and a bare asm("" ::: "memory") do
+  // not do this: both hold the loads in place, but the arithmetic has no
+  // memory side effect and no tie to either, so the scheduler sinks all of
+  // it below the last barrier and every gathered value is live at once,
+  // exactly as in the unsplit form (double: ~750 B/lane of scratch).
+  // Four statements of six operands: inline asm takes at most 30 operands.
+#define QA_ROUND_FENCE()                                                  \
+  _Pragma("unroll")                                                       \
+  for (int s_ = 0; s_ < 4; ++s_)                                          \
+    asm volatile("" : "+v"(acc[s_][0].re), "+v"(acc[s_][0].im),           \
+                      "+v"(acc[s_][1].re), "+v"(acc[s_][1].im),           \
+                      "+v"(acc[s_][2].re), "+v"(acc[s_][2].im) :: "memory");
+
+  if constexpr (ROUNDS == 1) {
     // all 8 gathers in flight, then all multiplies (max load ILP; ~210
-    // VGPRs -> 2 waves/SIMD)
+    // VGPRs -> 2 waves/SIMD at half)
     QA_GATHER(0)
     QA_GATHER(1)
     QA_GATHER(2)
     QA_GATHER(3)
     QA_MUL(0)
     QA_MUL(1)
+    QA_MUL(2)
+    QA_MUL(3)
+  } else if constexpr (ROUNDS == 2) {
+    // two 4-neighbor rounds halve the live half-spinor state so the
+    // LBW-wave occupancy cap is met without spilling — trades per-wave
+    // load ILP for thread-level parallelism
+    QA_GATHER(0)
+    QA_GATHER(1)
+    QA_MUL(0)
+    QA_MUL(1)
+    QA_ROUND_FENCE()
+    QA_GATHER(2)
+    QA_GATHER(3)
     QA_MUL(2)
     QA_MUL(3)
   } else {
-    // split-gather: two 4-neighbor rounds halve the live half-spinor
-    // state so the LBW-wave occupancy cap is met without spilling —
-    // trades per-wave ILP for thread-level parallelism.
+    // one direction per round: two spinors and two links live at a time
+    // (double: the only form that fits the register file, see
+    // qa_dslash_rounds)
+    static_assert(ROUNDS == 4);
     QA_GATHER(0)
-    QA_GATHER(1)
     QA_MUL(0)
+    QA_ROUND_FENCE()
+    QA_GATHER(1)
     QA_MUL(1)
-    // pin the round split: without this the scheduler hoists round-2 loads
-    // into round 1 and the live state spills right back to the 8-gather shape
-    __builtin_amdgcn_sched_barrier(0);
+    QA_ROUND_FENCE()
     QA_GATHER(2)
-    QA_GATHER(3)
     QA_MUL(2)
+    QA_ROUND_FENCE()
+    QA_GATHER(3)
     QA_MUL(3)
   }
+#undef QA_ROUND_FENCE
 #undef QA_GATHER
 #undef QA_MUL
 

@@ -35,7 +35,9 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
     if ((c.comm_mask >> m) & 1) n_ext += 2 * c.face_cb[m];
   int grid_ext = (int)((n_ext + blk - 1) / blk);
 
-  int waves = qa_dslash_waves();
+  // double has one form: its 4-round body at the 3-wave cap would spill
+  constexpr bool kCapForm = sizeof(R) != 8;
+  int waves = kCapForm ? qa_dslash_waves() : 0;
   int grid64 = (int)((c.Vcb + 63) / 64);
 
   // fused-epilogue kernels (k_dslash_wilson_clov_out2 / _xpay_dot): dispatched
@@ -93,18 +95,25 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
   }
 
 #define QA_LAUNCH(DAG, MODE, XPAY, KT)                                        \
-  if (c.kt == 3)                                                              \
-    hipLaunchKernelGGL((k_dslash_wilson_exterior<Prec, RECON, DAG, MODE, XPAY>), \
-                       dim3(grid_ext), dim3(blk), 0, st, out, in, g, cl, d,   \
-                       c.parity, a, x, gh, n_ext, br, bi);                    \
-  else if (waves == 3)                                                        \
-    hipLaunchKernelGGL((k_dslash_wilson<Prec, RECON, DAG, MODE, XPAY, KT, 3>),\
-                       dim3(grid64), dim3(64), 0, st, out, in, g, cl, d,      \
-                       c.parity, a, x, gh, br, bi);                           \
-  else                                                                        \
+  do {                                                                        \
+    if (c.kt == 3) {                                                          \
+      hipLaunchKernelGGL((k_dslash_wilson_exterior<Prec, RECON, DAG, MODE, XPAY>), \
+                         dim3(grid_ext), dim3(blk), 0, st, out, in, g, cl, d, \
+                         c.parity, a, x, gh, n_ext, br, bi);                  \
+      break;                                                                  \
+    }                                                                         \
+    if constexpr (kCapForm) {                                                 \
+      if (waves == 3) {                                                       \
+        hipLaunchKernelGGL((k_dslash_wilson<Prec, RECON, DAG, MODE, XPAY, KT, 3>), \
+                           dim3(grid64), dim3(64), 0, st, out, in, g, cl, d,  \
+                           c.parity, a, x, gh, br, bi);                       \
+        break;                                                                \
+      }                                                                       \
+    }                                                                         \
     hipLaunchKernelGGL((k_dslash_wilson<Prec, RECON, DAG, MODE, XPAY, KT>),   \
                        dim3(grid), dim3(blk), 0, st, out, in, g, cl, d,       \
-                       c.parity, a, x, gh, br, bi)
+                       c.parity, a, x, gh, br, bi);                           \
+  } while (0)
 
 #define QA_MODES(DAG, KT)                                                      \
   switch (c.mode) {                                                            \

@@ -19,6 +19,10 @@ inline int qa_dslash_block() { return qa_dslash_block_ref(); }
 // occupancy experiment: 0 = default (256-thread cap, ~2 waves/SIMD at the
 // measured 222 VGPRs), 3 = 64-thread workgroups with __launch_bounds__
 // forcing >= 3 waves/SIMD (VGPR cap 168). Only {0,3} are compiled.
+// Double has one form (4 gather rounds, ~220 VGPRs, which the cap would
+// spill): under 3 it launches its default kernel, and, the switch being
+// precision-blind, still goes without the fused epilogues
+// (qa_dslash_epilogue_ok), i.e. through the unfused launch sequence.
 inline int &qa_dslash_waves_ref() {
   static int w = [] {
     const char *e = getenv("QUDA_AMD_DSLASH_WAVES");
