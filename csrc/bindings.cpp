@@ -53,6 +53,52 @@ void check_launch(const char *what) {
   TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e));
 }
 
+LatDesc lat_of(const std::vector<int64_t> &dims, int64_t parity_offset,
+               int64_t Vcb) {
+  TORCH_CHECK(dims.size() == 4, "dims must hold the 4 local extents");
+  LatDesc l{};
+  for (int i = 0; i < 4; ++i) l.Xdim[i] = (int)dims[i];
+  l.parity_offset = (int)parity_offset;
+  l.Vcb = Vcb;
+  return l;
+}
+
+// the lists are read only when a dimension is partitioned
+GhostDesc ghost_of(const std::vector<at::Tensor> &ghost,
+                   const std::vector<at::Tensor> &ghost_nrm,
+                   const std::vector<int64_t> &face_cb, int64_t comm_mask) {
+  GhostDesc h{};
+  h.comm_mask = (int)comm_mask;
+  if (comm_mask) {
+    TORCH_CHECK(ghost.size() == 8 && ghost_nrm.size() == 8 && face_cb.size() == 4);
+    for (int k = 0; k < 8; ++k) {
+      h.ghost[k] = ptr_or_null(ghost[k]);
+      h.ghost_nrm[k] = (const float *)ptr_or_null(ghost_nrm[k]);
+    }
+    for (int k = 0; k < 4; ++k) h.face_cb[k] = face_cb[k];
+  }
+  return h;
+}
+
+// the Wilson kernels are split into one TU per precision
+auto wilson_launcher(int prec) {
+  switch (prec) {
+    case 0: return launch_dslash_wilson_double;
+    case 1: return launch_dslash_wilson_single;
+    case 2: return launch_dslash_wilson_half;
+    default: return launch_dslash_wilson_quarter;
+  }
+}
+
+auto pack_launcher(int prec) {
+  switch (prec) {
+    case 0: return launch_pack_face_double;
+    case 1: return launch_pack_face_single;
+    case 2: return launch_pack_face_half;
+    default: return launch_pack_face_quarter;
+  }
+}
+
 }  // namespace
 
 static void dslash_wilson(at::Tensor out, at::Tensor out_n, at::Tensor in,
@@ -78,24 +124,14 @@ static void dslash_wilson(at::Tensor out, at::Tensor out_n, at::Tensor in,
   TORCH_CHECK(out.is_contiguous() && in.is_contiguous() && gauge.is_contiguous());
   if (v_stride == 0) v_stride = Vcb;
   DslashCall c{};
-  c.comm_mask = (int)comm_mask;
+  c.halo = ghost_of(ghost, ghost_nrm, face_cb, comm_mask);
   c.kt = (int)kt;
-  if (comm_mask) {
-    TORCH_CHECK(ghost.size() == 8 && ghost_nrm.size() == 8 && face_cb.size() == 4);
-    for (int k = 0; k < 8; ++k) {
-      c.ghost[k] = ptr_or_null(ghost[k]);
-      c.ghost_nrm[k] = (const float *)ptr_or_null(ghost_nrm[k]);
-    }
-    for (int k = 0; k < 4; ++k) c.face_cb[k] = face_cb[k];
-  }
   c.out = field_of_off(out, out_n, v_stride, s_offset);
   c.in = field_of_off(in, in_n, v_stride, s_offset);
   c.x = field_of_off(x, x_n, v_stride, s_offset);
   c.gauge = gauge.data_ptr();
   c.clover = ptr_or_null(clover);
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.dagger = dagger;
   c.mode = (int)mode;
@@ -134,12 +170,7 @@ static void dslash_wilson(at::Tensor out, at::Tensor out_n, at::Tensor in,
               "dslash_wilson: no fused-epilogue kernel for this launch (out2: "
               "CLOV_POST, no dagger; dot: dagger PLAIN xpay; kt 0 or 1; "
               "default occupancy form)");
-  switch (prec_of(out)) {
-    case 0: launch_dslash_wilson_double(c, stream()); break;
-    case 1: launch_dslash_wilson_single(c, stream()); break;
-    case 2: launch_dslash_wilson_half(c, stream()); break;
-    case 3: launch_dslash_wilson_quarter(c, stream()); break;
-  }
+  wilson_launcher(prec_of(out))(c, stream());
   check_launch("dslash_wilson");
 }
 
@@ -168,21 +199,11 @@ static void dslash_wilson_mrhs(
     c.in[r] = field_of_off(in[r], in_n[r], v_stride, so);
     if (!x.empty()) c.x[r] = field_of_off(x[r], x_n[r], v_stride, so);
   }
-  c.comm_mask = (int)comm_mask;
+  c.halo = ghost_of(ghost, ghost_nrm, face_cb, comm_mask);
   c.kt = (int)kt;
-  if (comm_mask) {
-    TORCH_CHECK(ghost.size() == 8 && ghost_nrm.size() == 8 && face_cb.size() == 4);
-    for (int k = 0; k < 8; ++k) {
-      c.ghost[k] = ptr_or_null(ghost[k]);
-      c.ghost_nrm[k] = (const float *)ptr_or_null(ghost_nrm[k]);
-    }
-    for (int k = 0; k < 4; ++k) c.face_cb[k] = face_cb[k];
-  }
   c.gauge = gauge.data_ptr();
   c.clover = ptr_or_null(clover);
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.dagger = dagger;
   c.mode = (int)mode;
@@ -194,31 +215,36 @@ static void dslash_wilson_mrhs(
   check_launch("dslash_wilson_mrhs");
 }
 
-static void pack_face(at::Tensor dst, at::Tensor dst_nrm, at::Tensor in,
-                      at::Tensor in_n, std::vector<int64_t> dims,
-                      int64_t parity_offset, int64_t Vcb, int64_t parity,
-                      int64_t mu, int64_t s01, int64_t edge, int64_t Fcb,
-                      int64_t v_stride = 0, int64_t s_offset = 0) {
+// shared body of pack_face / pack_face_ptr (dst: tensor or raw peer pointer)
+static void pack_face_to(const char *what, void *dst, float *dst_nrm,
+                         const at::Tensor &in, const at::Tensor &in_n,
+                         const std::vector<int64_t> &dims,
+                         int64_t parity_offset, int64_t Vcb, int64_t parity,
+                         int64_t mu, int64_t s01, int64_t edge, int64_t Fcb,
+                         int64_t v_stride, int64_t s_offset) {
   PackCall c{};
   c.in = field_of_off(in, in_n, v_stride ? v_stride : Vcb, s_offset);
-  c.dst = dst.data_ptr();
-  c.dst_nrm = (float *)ptr_or_null(dst_nrm);
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.dst = dst;
+  c.dst_nrm = dst_nrm;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.mu = (int)mu;
   c.s01 = (int)s01;
   c.edge = (int)edge;
   c.Fcb = Fcb;
   c.prec = prec_of(in);
-  switch (c.prec) {
-    case 0: launch_pack_face_double(c, stream()); break;
-    case 1: launch_pack_face_single(c, stream()); break;
-    case 2: launch_pack_face_half(c, stream()); break;
-    case 3: launch_pack_face_quarter(c, stream()); break;
-  }
-  check_launch("pack_face");
+  pack_launcher(c.prec)(c, stream());
+  check_launch(what);
+}
+
+static void pack_face(at::Tensor dst, at::Tensor dst_nrm, at::Tensor in,
+                      at::Tensor in_n, std::vector<int64_t> dims,
+                      int64_t parity_offset, int64_t Vcb, int64_t parity,
+                      int64_t mu, int64_t s01, int64_t edge, int64_t Fcb,
+                      int64_t v_stride = 0, int64_t s_offset = 0) {
+  pack_face_to("pack_face", dst.data_ptr(), (float *)ptr_or_null(dst_nrm), in,
+               in_n, dims, parity_offset, Vcb, parity, mu, s01, edge, Fcb,
+               v_stride, s_offset);
 }
 
 static void pack_face_stag(at::Tensor dst, at::Tensor dst_nrm, at::Tensor in,
@@ -230,9 +256,7 @@ static void pack_face_stag(at::Tensor dst, at::Tensor dst_nrm, at::Tensor in,
   c.in = field_of(in, in_n, Vcb);
   c.dst = dst.data_ptr();
   c.dst_nrm = (float *)ptr_or_null(dst_nrm);
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.mu = (int)mu;
   c.edge = (int)edge;
@@ -260,26 +284,16 @@ static void dslash_staggered(at::Tensor out, at::Tensor out_n, at::Tensor in,
   c.x = field_of(x, x_n, Vcb);
   c.gauge = gauge.data_ptr();
   c.long_gauge = ptr_or_null(long_gauge);
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.xpay = xpay;
   c.a = a;
   c.b = b;
   c.recon = (int)recon;
-  c.comm_mask = (int)comm_mask;
+  c.halo = ghost_of(ghost, ghost_nrm, face_cb, comm_mask);
   c.kt = (int)kt;
   c.prec = prec_of(out);
   c.ghost_depth = (int)ghost_depth;
-  if (comm_mask) {
-    TORCH_CHECK(ghost.size() == 8 && ghost_nrm.size() == 8 && face_cb.size() == 4);
-    for (int k = 0; k < 8; ++k) {
-      c.ghost[k] = ptr_or_null(ghost[k]);
-      c.ghost_nrm[k] = (const float *)ptr_or_null(ghost_nrm[k]);
-    }
-    for (int k = 0; k < 4; ++k) c.face_cb[k] = face_cb[k];
-  }
   launch_dslash_staggered(c, stream());
   check_launch("dslash_staggered");
 }
@@ -515,9 +529,7 @@ static void dwf_fused(at::Tensor out, at::Tensor out_n, at::Tensor in,
   c.in = field_of(in, in_n, stride);
   c.x = xpay ? field_of(x, x_n, stride) : c.out;
   c.gauge = gauge.data_ptr();
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.Ls = (int)Ls;
   c.parity = (int)parity;
   c.dagger = dagger;
@@ -677,26 +689,9 @@ static void pack_face_ptr(int64_t dst, int64_t dst_nrm, at::Tensor in,
                           int64_t parity_offset, int64_t Vcb, int64_t parity,
                           int64_t mu, int64_t s01, int64_t edge, int64_t Fcb,
                           int64_t v_stride, int64_t s_offset) {
-  PackCall c{};
-  c.in = field_of_off(in, in_n, v_stride ? v_stride : Vcb, s_offset);
-  c.dst = (void *)(uintptr_t)dst;
-  c.dst_nrm = (float *)(uintptr_t)dst_nrm;
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
-  c.parity = (int)parity;
-  c.mu = (int)mu;
-  c.s01 = (int)s01;
-  c.edge = (int)edge;
-  c.Fcb = Fcb;
-  c.prec = prec_of(in);
-  switch (c.prec) {
-    case 0: launch_pack_face_double(c, stream()); break;
-    case 1: launch_pack_face_single(c, stream()); break;
-    case 2: launch_pack_face_half(c, stream()); break;
-    case 3: launch_pack_face_quarter(c, stream()); break;
-  }
-  check_launch("pack_face_ptr");
+  pack_face_to("pack_face_ptr", (void *)(uintptr_t)dst,
+               (float *)(uintptr_t)dst_nrm, in, in_n, dims, parity_offset, Vcb,
+               parity, mu, s01, edge, Fcb, v_stride, s_offset);
 }
 
 static void heatbath_sweep_dir(at::Tensor u, std::vector<int64_t> dims,
@@ -706,9 +701,7 @@ static void heatbath_sweep_dir(at::Tensor u, std::vector<int64_t> dims,
   TORCH_CHECK(u.is_contiguous() && u.scalar_type() == at::kComplexDouble);
   HeatbathCall c{};
   c.u = u.data_ptr();
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.parity = (int)parity;
   c.mu = (int)mu;
   c.beta_eff = beta_eff;
@@ -727,9 +720,7 @@ static void stout_smear_dir(at::Tensor out, at::Tensor in,
   StoutCall c{};
   c.out = out.data_ptr();
   c.in = in.data_ptr();
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.mu = (int)mu;
   c.rho = rho;
   launch_stout(c, stream());
@@ -743,9 +734,7 @@ static void flow_zmat_dir(at::Tensor Z, at::Tensor in,
   StoutCall c{};
   c.out = Z.data_ptr();
   c.in = in.data_ptr();
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.mu = (int)mu;
   c.rho = eps;
   launch_zmat(c, stream());
@@ -761,9 +750,7 @@ static void flow_expmul_dir(at::Tensor out, at::Tensor in, at::Tensor Zc,
   c.out = out.data_ptr();
   c.in = in.data_ptr();
   c.aux = Zc.data_ptr();
-  for (int i = 0; i < 4; ++i) c.Xdim[i] = (int)dims[i];
-  c.parity_offset = (int)parity_offset;
-  c.Vcb = Vcb;
+  c.lat = lat_of(dims, parity_offset, Vcb);
   c.mu = (int)mu;
   launch_expmul(c, stream());
   check_launch("expmul");

@@ -1,14 +1,14 @@
 // standalone clover apply TU
 #include "dslash_wilson.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 template <typename Prec>
 static void clover_apply_t(const CloverApplyCall &c, hipStream_t st) {
   // spinor strides come from the BlasField (slice views carry
   // v_stride/s_offset for 5-d doublet fields); the clover field is
   // always 4-d with stride c.Vcb
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
+  auto out = spinor_acc<Prec>(c.out);
+  auto in = spinor_acc<Prec>(c.in);
   CloverAcc<Prec> cl{(const typename Prec::Store *)c.clover, c.Vcb};
   int blk = 256;
   int grid = (int)((c.sites + blk - 1) / blk);
@@ -55,8 +55,8 @@ __global__ __launch_bounds__(256) void k_twist_apply(
 
 template <typename Prec>
 static void twist_apply_t(const TwistApplyCall &c, hipStream_t st) {
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
+  auto out = spinor_acc<Prec>(c.out);
+  auto in = spinor_acc<Prec>(c.in);
   int blk = 256;
   int grid = (int)((c.sites + blk - 1) / blk);
   using R = typename Prec::Real;

@@ -1,13 +1,13 @@
 // DWF/Moebius 5th-dimension TU (all precisions)
 #include "dslash_dwf.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 template <typename Prec>
 static void dwf5_t(const Dwf5Call &c, hipStream_t st) {
   using R = typename Prec::Real;
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  SpinorAcc<Prec> x{(typename Prec::Store *)c.x.data, (float *)c.x.norm, c.x.Vcb};
+  auto out = spinor_acc<Prec>(c.out);
+  auto in = spinor_acc<Prec>(c.in);
+  auto x = spinor_acc<Prec>(c.x);
   int blk = 256;
   R a = (R)c.a, al = (R)c.alpha, be = (R)c.beta, mf = (R)c.mf;
 
@@ -40,9 +40,9 @@ void launch_dwf5(const Dwf5Call &c, hipStream_t st) {
 template <typename Prec>
 static void zdwf5_t(const ZDwf5Call &c, const ZCoef *dzc, hipStream_t st) {
   using R = typename Prec::Real;
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  SpinorAcc<Prec> x{(typename Prec::Store *)c.x.data, (float *)c.x.norm, c.x.Vcb};
+  auto out = spinor_acc<Prec>(c.out);
+  auto in = spinor_acc<Prec>(c.in);
+  auto x = spinor_acc<Prec>(c.x);
   int blk = 256;
   R ar = (R)c.a_re, ai = (R)c.a_im;
 #define QA_Z5(XPAY)                                                           \
@@ -75,9 +75,9 @@ void launch_zdwf5(const ZDwf5Call &c, hipStream_t st) {
 template <typename Prec>
 static void eofa5_t(const Eofa5Call &c, hipStream_t st) {
   using R = typename Prec::Real;
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  SpinorAcc<Prec> x{(typename Prec::Store *)c.x.data, (float *)c.x.norm, c.x.Vcb};
+  auto out = spinor_acc<Prec>(c.out);
+  auto in = spinor_acc<Prec>(c.in);
+  auto x = spinor_acc<Prec>(c.x);
   EofaVec ev{};
   for (int s_ = 0; s_ < c.Ls && s_ < QA_ZMAX; ++s_) {
     ev.u[s_] = c.u[s_];

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "dslash_dwf_fused.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -44,23 +44,17 @@ const R *dwf_fused_w(const double *W, int Ls) {
 template <typename Prec, int RECON, int NS>
 bool dwf_fused_t(const DwfFusedCall &c, hipStream_t st) {
   using R = typename Prec::Real;
-  using S = typename Prec::Store;
-  // BlasField.Vcb carries the chunk stride Ls*Vcb of the 5-d fields
-  SpinorAcc<Prec> out{(S *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(S *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  SpinorAcc<Prec> x{(S *)c.x.data, (float *)c.x.norm, c.x.Vcb};
-  const long gpar = (long)GaugeAcc<Prec, RECON>::NCH * c.Vcb * Prec::W;
-  const auto *g0 = (const S *)c.gauge;
-  GaugeAcc<Prec, RECON> g{g0 + c.parity * gpar, g0 + (1 - c.parity) * gpar,
-                          c.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
+  // the fields carry the chunk stride Ls*Vcb; c.lat.Vcb is the 4-d volume
+  auto out = spinor_acc<Prec>(c.out), in = spinor_acc<Prec>(c.in),
+       x = spinor_acc<Prec>(c.x);
+  auto g = gauge_acc<Prec, RECON>(c.gauge, c.parity, c.lat.Vcb);
+  LatDims d = lat_dims(c.lat);
   const R *W = nullptr;
   if (c.W) {
     W = dwf_fused_w<R>(c.W, c.Ls);
     if (!W) return false;
   }
-  const unsigned grid = (unsigned)((c.Vcb + NS - 1) / NS);
+  const unsigned grid = (unsigned)((c.lat.Vcb + NS - 1) / NS);
   const unsigned blk = (unsigned)(NS * c.Ls);
   const size_t lds = c.W ? (size_t)24 * c.Ls * NS * sizeof(R) : 0;
   const R a = (R)c.a;

@@ -1,38 +1,23 @@
 // staggered dslash TU (all precisions; kernel is small)
 #include "dslash_staggered.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 template <typename Prec, int RECON>
 static void stag_launch(const StagDslashCall &c, hipStream_t st) {
   using R = typename Prec::Real;
-  StagAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.Vcb};
-  StagAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.Vcb};
-  StagAcc<Prec> x{(typename Prec::Store *)c.x.data, (float *)c.x.norm, c.Vcb};
-  const long gpar = (long)GaugeAcc<Prec, RECON>::NCH * c.Vcb * Prec::W;
-  const auto *g0 = (const typename Prec::Store *)c.gauge;
-  GaugeAcc<Prec, RECON> g{g0 + c.parity * gpar, g0 + (1 - c.parity) * gpar,
-                          c.Vcb};
-  const typename Prec::Store *l0 = (const typename Prec::Store *)c.long_gauge;
-  const long lpar = (long)GaugeAcc<Prec, 18>::NCH * c.Vcb * Prec::W;
+  auto out = stag_acc<Prec>(c.out), in = stag_acc<Prec>(c.in),
+       x = stag_acc<Prec>(c.x);
+  auto g = gauge_acc<Prec, RECON>(c.gauge, c.parity, c.lat.Vcb);
   // 3-hop neighbors flip parity too (odd shift): bwd long links also read
   // the other parity block's fwd slots
-  GaugeAcc<Prec, 18> lng{l0 ? l0 + c.parity * lpar : nullptr,
-                         l0 ? l0 + (1 - c.parity) * lpar : nullptr, c.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset, c.Vcb};
-  GhostAcc<Prec, 6> gh{};
-  gh.mask = c.comm_mask;
-  for (int k = 0; k < 8; ++k) {
-    gh.buf[k] = (const typename Prec::Store *)c.ghost[k];
-    gh.nrm[k] = c.ghost_nrm[k];
-  }
-  for (int k = 0; k < 4; ++k) gh.Fcb[k] = c.face_cb[k];
-  gh.depth = c.ghost_depth > 0 ? c.ghost_depth : 1;
+  auto lng = gauge_acc<Prec, 18>(c.long_gauge, c.parity, c.lat.Vcb);
+  LatDims d = lat_dims(c.lat);
+  auto gh = ghost_acc<GhostAcc<Prec, 6>>(
+      c.halo, c.ghost_depth > 0 ? c.ghost_depth : 1);
   int blk = 256;
-  int grid = (int)((c.Vcb + blk - 1) / blk);
+  int grid = (int)((c.lat.Vcb + blk - 1) / blk);
   R a = (R)c.a, b = (R)c.b;
-  long n_ext = 0;
-  for (int m = 0; m < 4; ++m)
-    if ((c.comm_mask >> m) & 1) n_ext += 2 * c.face_cb[m];
+  long n_ext = exterior_threads(c.halo);
   int grid_ext = (int)((n_ext + blk - 1) / blk);
 
 #define QA_SLAUNCH(XPAY, KT)                                                   \
@@ -74,8 +59,8 @@ void launch_dslash_staggered(const StagDslashCall &c, hipStream_t st) {
 
 template <typename Prec>
 static void stag_pack(const PackCall &c, hipStream_t st) {
-  StagAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset, c.Vcb};
+  auto in = stag_acc<Prec>(c.in);
+  LatDims d = lat_dims(c.lat);
   int blk = 256;
   int depth = c.depth > 0 ? c.depth : 1;
   long n = c.Fcb * depth;

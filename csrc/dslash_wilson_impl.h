@@ -1,44 +1,31 @@
-#include <cstdlib>
 // Shared runtime->template dispatch for the Wilson dslash TUs.
 #pragma once
+#include <cstdlib>
+
 #include "dslash_wilson.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 template <typename Prec, int RECON>
 static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
   using R = typename Prec::Real;
-  // BlasField.Vcb carries the CHUNK STRIDE (= Ls*Vcb for a 5-d field whose
-  // s-slice is addressed via a pointer offset); c.Vcb is the 4-d cb volume
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.out.data, (float *)c.out.norm, c.out.Vcb};
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  SpinorAcc<Prec> x{(typename Prec::Store *)c.x.data, (float *)c.x.norm, c.x.Vcb};
-  // parity-offset the stencil gauge base: [2][NCH][V][W]
-  const long gpar = (long)GaugeAcc<Prec, RECON>::NCH * c.Vcb * Prec::W;
-  const auto *g0 = (const typename Prec::Store *)c.gauge;
-  GaugeAcc<Prec, RECON> g{g0 + c.parity * gpar, g0 + (1 - c.parity) * gpar,
-                          c.Vcb};
-  CloverAcc<Prec> cl{(const typename Prec::Store *)c.clover, c.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset, c.Vcb};
-  GhostAcc<Prec> gh{};
-  gh.mask = c.comm_mask;
-  for (int k = 0; k < 8; ++k) {
-    gh.buf[k] = (const typename Prec::Store *)c.ghost[k];
-    gh.nrm[k] = c.ghost_nrm[k];
-  }
-  for (int k = 0; k < 4; ++k) gh.Fcb[k] = c.face_cb[k];
+  const long Vcb = c.lat.Vcb;  // 4-d cb volume (the fields carry their stride)
+  auto out = spinor_acc<Prec>(c.out), in = spinor_acc<Prec>(c.in),
+       x = spinor_acc<Prec>(c.x);
+  auto g = gauge_acc<Prec, RECON>(c.gauge, c.parity, Vcb);
+  CloverAcc<Prec> cl{(const typename Prec::Store *)c.clover, Vcb};
+  LatDims d = lat_dims(c.lat);
+  auto gh = ghost_acc<GhostAcc<Prec>>(c.halo);
   int blk = qa_dslash_block();
-  int grid = (int)((c.Vcb + blk - 1) / blk);
+  int grid = (int)((Vcb + blk - 1) / blk);
   R a = (R)c.a;
   R br = (R)c.b_re, bi = (R)c.b_im;
-  long n_ext = 0;
-  for (int m = 0; m < 4; ++m)
-    if ((c.comm_mask >> m) & 1) n_ext += 2 * c.face_cb[m];
+  long n_ext = exterior_threads(c.halo);
   int grid_ext = (int)((n_ext + blk - 1) / blk);
 
   // double has one form: its 4-round body at the 3-wave cap would spill
   constexpr bool kCapForm = sizeof(R) != 8;
   int waves = kCapForm ? qa_dslash_waves() : 0;
-  int grid64 = (int)((c.Vcb + 63) / 64);
+  int grid64 = (int)((Vcb + 63) / 64);
 
   // fused-epilogue kernels (k_dslash_wilson_clov_out2 / _xpay_dot): dispatched
   // apart from the QA_MODES matrix so only the combinations MdagM uses are
@@ -46,8 +33,7 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
   // with dot; kt 0/1, default occupancy form only. The caller checked
   // qa_dslash_epilogue_ok.
   if (c.out2.data || c.y.data) {
-    SpinorAcc<Prec> out2{(typename Prec::Store *)c.out2.data, (float *)c.out2.norm, c.out2.Vcb};
-    SpinorAcc<Prec> y{(typename Prec::Store *)c.y.data, (float *)c.y.norm, c.y.Vcb};
+    auto out2 = spinor_acc<Prec>(c.out2), y = spinor_acc<Prec>(c.y);
 #define QA_EPI_LAUNCH(KERNEL, KT, ...)                                         \
   hipLaunchKernelGGL((KERNEL<Prec, RECON, __VA_ARGS__, KT>), dim3(grid),       \
                      dim3(blk), 0, st, out, in, g, cl, d, c.parity, a, x, gh,  \
@@ -75,18 +61,35 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
   // LDS-tiled path (half/quarter, local, 4-d, tile-divisible dims,
   // PLAIN/CLOV_POST/TWIST_POST): see k_dslash_wilson_lds
   if constexpr (Prec::has_norm) {
-    bool lds_ok = qa_dslash_lds() && c.kt == 0 && c.comm_mask == 0 &&
-                  c.in.Vcb == c.Vcb && c.out.Vcb == c.Vcb &&
+    const int *X = c.lat.Xdim;
+    bool lds_ok = qa_dslash_lds() && c.kt == 0 && c.halo.comm_mask == 0 &&
+                  c.in.Vcb == Vcb && c.out.Vcb == Vcb &&
                   (c.mode == PLAIN || c.mode == CLOV_POST ||
                    c.mode == TWIST_POST) &&
-                  c.Xdim[0] % LdsTile::BX == 0 &&
-                  c.Xdim[1] % LdsTile::BY == 0 &&
-                  c.Xdim[2] % LdsTile::BZ == 0 && c.Xdim[3] % LdsTile::BT == 0;
+                  X[0] % LdsTile::BX == 0 && X[1] % LdsTile::BY == 0 &&
+                  X[2] % LdsTile::BZ == 0 && X[3] % LdsTile::BT == 0;
     if (lds_ok) {
-      long ntile = ((long)c.Xdim[0] / LdsTile::BX) * (c.Xdim[1] / LdsTile::BY) *
-                   (c.Xdim[2] / LdsTile::BZ) * (c.Xdim[3] / LdsTile::BT);
-#define QA_LDS_LAUNCH(DAG, MODE, XPAY)                                              hipLaunchKernelGGL((k_dslash_wilson_lds<Prec, RECON, DAG, MODE, XPAY>),                          dim3((unsigned)ntile), dim3(256), 0, st, out, in, g,                          cl, d, c.parity, a, x, br, bi)
-#define QA_LDS_MODES(DAG)                                                           switch (c.mode) {                                                               case PLAIN:                                                                     if (c.xpay) QA_LDS_LAUNCH(DAG, PLAIN, true);                                  else QA_LDS_LAUNCH(DAG, PLAIN, false);                                        break;                                                                      case CLOV_POST:                                                                 if (c.xpay) QA_LDS_LAUNCH(DAG, CLOV_POST, true);                              else QA_LDS_LAUNCH(DAG, CLOV_POST, false);                                    break;                                                                      case TWIST_POST:                                                                if (c.xpay) QA_LDS_LAUNCH(DAG, TWIST_POST, true);                             else QA_LDS_LAUNCH(DAG, TWIST_POST, false);                                   break;                                                                    }
+      long ntile = ((long)X[0] / LdsTile::BX) * (X[1] / LdsTile::BY) *
+                   (X[2] / LdsTile::BZ) * (X[3] / LdsTile::BT);
+#define QA_LDS_LAUNCH(DAG, MODE, XPAY)                                         \
+  hipLaunchKernelGGL((k_dslash_wilson_lds<Prec, RECON, DAG, MODE, XPAY>),      \
+                     dim3((unsigned)ntile), dim3(256), 0, st, out, in, g, cl,  \
+                     d, c.parity, a, x, br, bi)
+#define QA_LDS_MODES(DAG)                                                      \
+  switch (c.mode) {                                                            \
+    case PLAIN:                                                                \
+      if (c.xpay) QA_LDS_LAUNCH(DAG, PLAIN, true);                             \
+      else QA_LDS_LAUNCH(DAG, PLAIN, false);                                   \
+      break;                                                                   \
+    case CLOV_POST:                                                            \
+      if (c.xpay) QA_LDS_LAUNCH(DAG, CLOV_POST, true);                         \
+      else QA_LDS_LAUNCH(DAG, CLOV_POST, false);                               \
+      break;                                                                   \
+    case TWIST_POST:                                                           \
+      if (c.xpay) QA_LDS_LAUNCH(DAG, TWIST_POST, true);                        \
+      else QA_LDS_LAUNCH(DAG, TWIST_POST, false);                              \
+      break;                                                                   \
+  }
       if (!c.dagger) { QA_LDS_MODES(false) } else { QA_LDS_MODES(true) }
 #undef QA_LDS_MODES
 #undef QA_LDS_LAUNCH
@@ -150,8 +153,8 @@ static void dslash_launch_all(const DslashCall &c, hipStream_t st) {
 
 template <typename Prec>
 static void pack_launch(const PackCall &c, hipStream_t st) {
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.in.data, (float *)c.in.norm, c.in.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset, c.Vcb};
+  auto in = spinor_acc<Prec>(c.in);
+  LatDims d = lat_dims(c.lat);
   int blk = 256;
   int grid = (int)((c.Fcb + blk - 1) / blk);
   auto *dst = (typename Prec::Store *)c.dst;

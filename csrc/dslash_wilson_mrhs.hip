@@ -1,6 +1,6 @@
 // Multi-RHS Wilson dslash TU (all precisions; NRHS 2 and 4).
 #include "dslash_wilson_mrhs.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 template <typename Prec, int RECON, int NRHS>
 static void mrhs_launch(const DslashMrhsCall &c, hipStream_t st) {
@@ -15,22 +15,12 @@ static void mrhs_launch(const DslashMrhsCall &c, hipStream_t st) {
     ptr.x_n[r] = (const float *)c.x[r].norm;
   }
   long Vs = c.out[0].Vcb;  // chunk stride
-  const long gpar = (long)GaugeAcc<Prec, RECON>::NCH * c.Vcb * Prec::W;
-  const auto *g0 = (const S *)c.gauge;
-  GaugeAcc<Prec, RECON> g{g0 + c.parity * gpar, g0 + (1 - c.parity) * gpar,
-                          c.Vcb};
-  CloverAcc<Prec> cl{(const S *)c.clover, c.Vcb};
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
-  GhostAcc<Prec> gh{};
-  gh.mask = c.comm_mask;
-  for (int k = 0; k < 8; ++k) {
-    gh.buf[k] = (const S *)c.ghost[k];
-    gh.nrm[k] = c.ghost_nrm[k];
-  }
-  for (int k = 0; k < 4; ++k) gh.Fcb[k] = c.face_cb[k];
+  auto g = gauge_acc<Prec, RECON>(c.gauge, c.parity, c.lat.Vcb);
+  CloverAcc<Prec> cl{(const S *)c.clover, c.lat.Vcb};
+  LatDims d = lat_dims(c.lat);
+  auto gh = ghost_acc<GhostAcc<Prec>>(c.halo);
   int blk = qa_dslash_block();
-  int grid = (int)((c.Vcb + blk - 1) / blk);
+  int grid = (int)((c.lat.Vcb + blk - 1) / blk);
   typename Prec::Real a = (typename Prec::Real)c.a;
 
 #define QA_M_LAUNCH(DAG, MODE, XPAY, KT)                                      \

@@ -88,7 +88,7 @@ struct GhostAcc {
   }
 
   // batched-halo view: rhs slice r of a [n_rhs][NCH][depth*Fcb][GW]
-  // buffer (parallel/halo.py BatchSpinorHalo — buf[] points at slice 0)
+  // buffer (parallel/halo.py SpinorHalo n_slab — buf[] points at slice 0)
   __device__ __forceinline__ void load_r(cplx<R> (&h)[2][3], int mu, int dir,
                                          long f, int r) const {
     static_assert(NCOMP == 12);

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -238,9 +238,8 @@ __global__ __launch_bounds__(128) void k_heatbath(
 }
 
 void launch_heatbath(const HeatbathCall &c, hipStream_t st) {
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
-  int grid = (int)((c.Vcb + 127) / 128);
+  LatDims d = lat_dims(c.lat);
+  int grid = (int)((c.lat.Vcb + 127) / 128);
   hipLaunchKernelGGL(k_heatbath, dim3(grid), dim3(128), 0, st, (cd *)c.u, d,
                      c.parity, c.mu, c.beta_eff, c.seed, c.mode);
 }
@@ -394,9 +393,8 @@ __global__ __launch_bounds__(128) void k_stout(
 }
 
 void launch_stout(const StoutCall &c, hipStream_t st) {
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
-  int grid = (int)((2 * c.Vcb + 127) / 128);
+  LatDims d = lat_dims(c.lat);
+  int grid = (int)((2 * c.lat.Vcb + 127) / 128);
   hipLaunchKernelGGL(k_stout, dim3(grid), dim3(128), 0, st, (cd *)c.out,
                      (const cd *)c.in, d, c.mu, c.rho);
 }
@@ -493,17 +491,15 @@ __global__ __launch_bounds__(128) void k_expmul(
 }
 
 void launch_zmat(const StoutCall &c, hipStream_t st) {
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
-  int grid = (int)((2 * c.Vcb + 127) / 128);
+  LatDims d = lat_dims(c.lat);
+  int grid = (int)((2 * c.lat.Vcb + 127) / 128);
   hipLaunchKernelGGL(k_zmat, dim3(grid), dim3(128), 0, st, (cd *)c.out,
                      (const cd *)c.in, d, c.mu, c.rho);
 }
 
 void launch_expmul(const StoutCall &c, hipStream_t st) {
-  LatDims d{{c.Xdim[0], c.Xdim[1], c.Xdim[2], c.Xdim[3]}, c.parity_offset,
-            c.Vcb};
-  int grid = (int)((2 * c.Vcb + 127) / 128);
+  LatDims d = lat_dims(c.lat);
+  int grid = (int)((2 * c.lat.Vcb + 127) / 128);
   hipLaunchKernelGGL(k_expmul, dim3(grid), dim3(128), 0, st, (cd *)c.out,
                      (const cd *)c.in, (const cd *)c.aux, d, c.mu);
 }

@@ -94,27 +94,37 @@ void launch_convert(const BlasField &dst, int pdst, const BlasField &src,
                     int psrc, long sites, int ncomp, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// descriptors shared by the stencil-family call structs; launch_setup.h turns
+// them into the device-side LatDims / GhostAcc
+struct LatDesc {
+  int Xdim[4];
+  int parity_offset;
+  long Vcb;  // cb volume
+};
+
+// ghost recv buffers per [2*mu+dir] (dir 1 = from +mu neighbor); null when
+// mask bit mu unset. comm_mask==0 => pure-local kernel.
+struct GhostDesc {
+  const void *ghost[8];
+  const float *ghost_nrm[8];
+  long face_cb[4];
+  int comm_mask;
+};
+
 struct DslashCall {
   // single-parity field views (data points at the parity slice)
   BlasField out, in, x;    // x used when xpay / CLOV_X
   const void *gauge;       // [mu][par][nch][Vcb][2]
   const void *clover;      // packed [par][nch][Vcb][W] (A or A^-1 slice)
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int parity;
   bool dagger;
-  int mode;   // 0 PLAIN, 1 CLOV_POST, 2 CLOV_X
+  int mode;   // CloverMode (csrc/dslash_wilson.h)
   bool xpay;
   double a;
   double b_re, b_im;  // twist scalar for TWIST_*/CLOVTW_* modes
   int recon;  // 18 or 12
-  // halo: ghost recv buffers per [2*mu+dir] (dir 1 = from +mu neighbor);
-  // null when mask bit mu unset. comm_mask==0 => pure-local kernel.
-  const void *ghost[8];
-  const float *ghost_nrm[8];
-  long face_cb[4];
-  int comm_mask;
+  GhostDesc halo;
   int kt;  // 0 local, 1 fused, 2 interior, 3 exterior (csrc/dslash_wilson.h)
   // fused epilogues (kt 0/1 only, never both at once; null = off):
   //   out2       : CLOV_POST, !dagger: out2 = A_clov * (out as stored)
@@ -151,20 +161,14 @@ struct DslashMrhsCall {
   BlasField out[QA_MRHS_MAX], in[QA_MRHS_MAX], x[QA_MRHS_MAX];
   const void *gauge;
   const void *clover;
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int parity;
   bool dagger;
   int mode;
   bool xpay;
   double a;
   int recon;
-  // batched ghosts: slice-0 base per [2*mu+dir]; kernel offsets by rhs
-  const void *ghost[8];
-  const float *ghost_nrm[8];
-  long face_cb[4];
-  int comm_mask;
+  GhostDesc halo;  // slice-0 base per face; the kernel offsets by rhs
   int kt;  // 0 local, 1 fused, 2 interior (exterior runs per-RHS)
   int prec;
 };
@@ -175,9 +179,7 @@ struct PackCall {
   BlasField in;       // dslash input spinor (single parity view)
   void *dst;
   float *dst_nrm;     // half only
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int parity;         // parity of `in`
   int mu;
   int s01;            // projector sign index (dir XOR dagger)
@@ -216,17 +218,12 @@ struct StagDslashCall {
   BlasField out, in, x;  // single-parity views
   const void *gauge;     // stencil layout, like DslashCall
   const void *long_gauge;  // Naik links (stencil layout, shift=3, recon 18); null = naive
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int parity;
   bool xpay;
   double a, b;  // out = [a*x +] b*(D in); dagger folds into b
   int recon;
-  const void *ghost[8];
-  const float *ghost_nrm[8];
-  long face_cb[4];
-  int comm_mask;
+  GhostDesc halo;
   int kt;  // 0 local, 1 fused, 2 interior, 3 exterior
   int prec;
   int ghost_depth;  // 1, or 3 when long links cross rank boundaries
@@ -254,9 +251,7 @@ void launch_dwf5(const Dwf5Call &c, hipStream_t st);
 struct DwfFusedCall {
   BlasField out, in, x;  // 5-d single-parity fields (Vcb = chunk stride Ls*Vcb4)
   const void *gauge;     // stencil layout, like DslashCall
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;              // 4-d cb volume
+  LatDesc lat;           // Vcb = 4-d cb volume
   int Ls;                // 1..QA_DWF_FUSED_LS_MAX
   int parity;
   bool dagger;
@@ -297,9 +292,7 @@ void launch_coarse_dslash_mfma(const CoarseMfmaCall &c, hipStream_t st);
 // native heatbath / overrelaxation sweep (csrc/heatbath.hip)
 struct HeatbathCall {
   void *u;  // [4][2][Vcb][3][3] complex double (oracle layout)
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int parity;
   int mu;
   double beta_eff;
@@ -312,9 +305,7 @@ struct StoutCall {
   void *out;       // [4][2][Vcb][3][3] complex double
   const void *in;
   const void *aux;  // expmul: the combined Z tensor
-  int Xdim[4];
-  int parity_offset;
-  long Vcb;
+  LatDesc lat;
   int mu;
   double rho;      // zmat: the eps scale
 };

@@ -10,8 +10,7 @@
 //   V           [Na][B][12][Nv] complex, aggregate order: restrict, ortho
 //   coarse      [Na][2][Nv] complex of the field's real type
 //   agg_of_site [G] int32, site_tab [Na][B] int32 (fine site of (a, b))
-#include "common.h"
-#include "launchers.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -236,8 +235,7 @@ template <typename Prec>
 void prolong_t(const TransferCall &c, hipStream_t st) {
   using R = typename Prec::Real;
   const long G = 2 * c.field.Vcb;
-  SpinorAcc<Prec> out{(typename Prec::Store *)c.field.data, nullptr,
-                      c.field.Vcb};
+  auto out = spinor_acc<Prec>(c.field);  // double/single: no norm
   const int T = 64;  // one wave per workgroup spreads small lattices widest
   hipLaunchKernelGGL(k_transfer_prolong<Prec>, dim3((unsigned)((G + T - 1) / T)),
                      dim3(T), 0, st, out, (const cplx<R> *)c.coarse,
@@ -248,8 +246,7 @@ template <typename Prec>
 void restrict_t(const TransferCall &c, hipStream_t st) {
   using R = typename Prec::Real;
   const long G = 2 * c.field.Vcb;
-  SpinorAcc<Prec> in{(typename Prec::Store *)c.field.data, nullptr,
-                     c.field.Vcb};
+  auto in = spinor_acc<Prec>(c.field);
   const long ntile = (c.Nv + QA_TR_MAXT - 1) / QA_TR_MAXT;
   hipLaunchKernelGGL(k_transfer_restrict<Prec>,
                      dim3((unsigned)(c.Na * 2 * ntile)), dim3(QA_TR_MAXT), 0,

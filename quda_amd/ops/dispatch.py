@@ -115,17 +115,73 @@ def on_gpu(*fields) -> bool:
     return any(f is not None and f.device.type == "cuda" for f in fields)
 
 
-def _empty(dev):
-    return torch.empty(0, dtype=torch.float32, device=dev)
+_EMPTY = {}
+
+
+def empty_tensor(dtype, device) -> torch.Tensor:
+    """The shared zero-size placeholder of (dtype, device): what a launch
+    passes where the extension takes a tensor it will not read."""
+    t = _EMPTY.get((dtype, device))
+    if t is None:
+        t = _EMPTY[(dtype, device)] = torch.empty(0, dtype=dtype,
+                                                  device=device)
+    return t
 
 
 def norm_or_empty(f: Optional[SpinorField]):
     if f is None or f.norm is None:
-        return _empty("cpu" if f is None else f.device)
+        return empty_tensor(torch.float32, "cpu" if f is None else f.device)
     return f.norm
 
 
 from ..fields.gauge import RECON_COMPS
+
+_NO_HALO = ([], [], [], 0)  # (ghost[8], ghost_nrm[8], face_cb[4], comm_mask)
+
+
+def _launch_wilson(ext, out, inp, gauge, cl_t, x, parity, dagger, mode, a,
+                   halo=_NO_HALO, kt=0, twist=(0.0, 0.0), v_stride=0,
+                   s_offset=0, **epilogue):
+    """The raw ext.dslash_wilson launch. halo = a halo's ghost_args() +
+    (comm_mask,); v_stride / s_offset address one 4-d slice of 5-d fields;
+    epilogue = the out2 / dot keywords of the fused-epilogue kernels."""
+    geo = out.geo
+    xf = x if x is not None else out
+    ghosts, nrms, face_cb, comm_mask = halo
+    ext.dslash_wilson(
+        out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
+        gauge.data, cl_t, xf.data, norm_or_empty(xf), list(geo.dims),
+        geo.parity_offset, geo.volume_cb, parity, bool(dagger), mode,
+        x is not None, float(a), RECON_COMPS[gauge.reconstruct], ghosts, nrms,
+        face_cb, comm_mask, kt, float(twist[0]), float(twist[1]), v_stride,
+        s_offset, **epilogue)
+
+
+def _launch_wilson_mrhs(ext, outs, inps, gauge, cl_t, xs, parity, dagger,
+                        mode, a, halo=_NO_HALO, kt=0, v_stride=0,
+                        s_offsets=()):
+    """The raw ext.dslash_wilson_mrhs launch on 2 or 4 sides (xs empty: no
+    xpay). The ghosts of `halo` are the group's base slice of a slab halo;
+    v_stride / s_offsets address 4-d slices of one 5-d field per side."""
+    geo = outs[0].geo
+    ghosts, nrms, face_cb, comm_mask = halo
+    ext.dslash_wilson_mrhs(
+        [o.data for o in outs], [norm_or_empty(o) for o in outs],
+        [i.data for i in inps], [norm_or_empty(i) for i in inps],
+        gauge.data, cl_t, [x.data for x in xs],
+        [norm_or_empty(x) for x in xs], list(geo.dims), geo.parity_offset,
+        geo.volume_cb, parity, bool(dagger), mode, bool(xs), float(a),
+        RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb, comm_mask, kt,
+        v_stride, list(s_offsets))
+
+
+def _oracle_halo(gauge, parity: int, mask: int, psi_ghosts) -> dict:
+    """Halo dict of the reference stencils: exchanged spinor faces plus the
+    backward ghost links of every partitioned dim."""
+    from ..parallel.halo import active_dims
+    return {"mask": mask, "psi": psi_ghosts,
+            "u_bwd": {mu: gauge.bwd_ghost(mu, parity)
+                      for mu in active_dims(mask)}}
 
 _AUTOTUNE = None
 
@@ -230,12 +286,11 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
                  f"{epi}")
     if on_gpu(out, inp):
         ext = hip_ext()
-        cl_t = torch.empty(0, dtype=out.data.dtype, device=out.device)
+        cl_t = empty_tensor(out.data.dtype, out.device)
         if mode in (CLOV_POST, CLOV_X, CLOVTW_X):
             cl_t = clover.inv_data if clover_inverse else clover.data
-        xf = x if x is not None else out
 
-        def launch(kt, ghosts=[], nrms=[], face_cb=[], result=dot_result):
+        def launch(kt, halo=_NO_HALO, result=dot_result):
             kw = {}
             if out2 is not None:
                 kw = dict(out2=out2.data, out2_n=norm_or_empty(out2))
@@ -243,13 +298,8 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
                 kw = dict(dot_y=dot_with.data, dot_y_n=norm_or_empty(dot_with),
                           dot_result=result, dot_slots=int(dot_slots),
                           dot_stride=int(dot_stride))
-            ext.dslash_wilson(
-                out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
-                gauge.data, cl_t, xf.data, norm_or_empty(xf),
-                list(geo.dims), geo.parity_offset, geo.volume_cb, parity,
-                bool(dagger), mode, xpay, float(a),
-                RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb,
-                mask if kt else 0, kt, float(twist[0]), float(twist[1]), **kw)
+            _launch_wilson(ext, out, inp, gauge, cl_t, x, parity, dagger,
+                           mode, a, halo, kt, twist, **kw)
 
         if not mask:
             # autotuned workgroup size (ref: lib/tune.cpp tuneLaunch —
@@ -294,21 +344,21 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
             from ..parallel.ipc_halo import get_ipc_halo
             hi = get_ipc_halo(geo, inp.precision, inp.device, mask)
             hi.pack_remote(ext, inp, 1 - parity, bool(dagger))
-            ghosts, nrms, face_cb = hi.ghost_args()
-            launch(2, ghosts, nrms, face_cb)   # interior
+            halo = hi.ghost_args() + (mask,)
+            launch(2, halo)   # interior
             hi.complete()
-            launch(3, ghosts, nrms, face_cb)   # exterior
+            launch(3, halo)   # exterior
             return out
 
         def run_halo():
             h.pack(ext, inp, 1 - parity, bool(dagger))
-            ghosts, nrms, face_cb = h.ghost_args()
+            halo = h.ghost_args() + (mask,)
             if dslash_policy() == "fused":
                 h.exchange()
-                launch(1, ghosts, nrms, face_cb)
+                launch(1, halo)
             else:
                 reqs = h.exchange_start()
-                launch(2, ghosts, nrms, face_cb)   # interior
+                launch(2, halo)   # interior
                 if aux_worker is not None:
                     # independent work queued into the comms window (ref:
                     # dslash::aux_worker lib/dslash_quda.cu:73 — the
@@ -316,7 +366,7 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
                     aux_worker()
                 for r in reqs:
                     r.wait()
-                launch(3, ghosts, nrms, face_cb)   # exterior
+                launch(3, halo)   # exterior
 
         import os
         if _autotune_on() and os.environ.get("QUDA_AMD_BLOCKING_COMMS",
@@ -335,13 +385,9 @@ def dslash_wilson(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     psi = inp.to_complex()[0]
     halo = None
     if mask:
-        from ..parallel.halo import active_dims, exchange_psi_oracle
-        halo = {
-            "mask": mask,
-            "psi": exchange_psi_oracle(psi, geo, 1 - parity, mask),
-            "u_bwd": {mu: gauge.bwd_ghost(mu, parity)
-                      for mu in active_dims(mask)},
-        }
+        from ..parallel.halo import exchange_psi_oracle
+        halo = _oracle_halo(gauge, parity, mask,
+                            exchange_psi_oracle(psi, geo, 1 - parity, mask))
     res = ref.dslash_wilson_parity(u, psi, geo, parity, dagger, halo=halo)
     if mode == CLOV_POST:
         A = clover.to_complex(inverse=clover_inverse)[parity]
@@ -427,7 +473,7 @@ def dslash_wilson_batch(outs, inps, gauge: GaugeField, parity: int,
     mask = comms.comm_mask()
     xpay = xs is not None
 
-    def per_rhs(i, kt=None, ghosts=None, nrms=None, face_cb=None, h=None):
+    def per_rhs(i):
         dslash_wilson(outs[i], inps[i], gauge, parity, dagger=dagger,
                       a=a, x=xs[i] if xs else None, mode=mode,
                       clover=clover, clover_inverse=clover_inverse)
@@ -442,53 +488,39 @@ def dslash_wilson_batch(outs, inps, gauge: GaugeField, parity: int,
 
     ext = hip_ext()
     groups, rem0 = _mrhs_groups(n)
-    cl_t = torch.empty(0, dtype=outs[0].data.dtype, device=outs[0].device)
+    cl_t = empty_tensor(outs[0].data.dtype, outs[0].device)
     if mode == CLOV_POST:
         cl_t = clover.inv_data if clover_inverse else clover.data
 
-    def launch_group(r0, g, kt, ghosts, nrms, face_cb):
+    def launch_group(r0, g, kt, halo=_NO_HALO):
         sl = slice(r0, r0 + g)
-        xg = xs[sl] if xs else []
-        ext.dslash_wilson_mrhs(
-            [o.data for o in outs[sl]], [norm_or_empty(o) for o in outs[sl]],
-            [i_.data for i_ in inps[sl]],
-            [norm_or_empty(i_) for i_ in inps[sl]],
-            gauge.data, cl_t,
-            [x_.data for x_ in xg], [norm_or_empty(x_) for x_ in xg],
-            list(geo.dims), geo.parity_offset, geo.volume_cb, parity,
-            bool(dagger), mode, xpay, float(a),
-            RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb,
-            mask if kt else 0, kt)
+        _launch_wilson_mrhs(ext, outs[sl], inps[sl], gauge, cl_t,
+                            xs[sl] if xs else [], parity, dagger, mode, a,
+                            halo, kt)
 
     if not mask:
         for r0, g in groups:
-            launch_group(r0, g, 0, [], [], [])
+            launch_group(r0, g, 0)
         for i in range(rem0, n):
             per_rhs(i)
         return outs
 
-    from ..parallel.halo import get_batch_halo
-    h = get_batch_halo(geo, inps[0].precision, inps[0].device, mask, n)
+    from ..parallel.halo import get_spinor_halo
+    h = get_spinor_halo(geo, inps[0].precision, inps[0].device, mask,
+                        n_slab=n)
     for i in range(n):
-        h.pack_one(ext, i, inps[i], 1 - parity, bool(dagger))
+        h.pack(ext, inps[i], 1 - parity, bool(dagger), slab=i)
     reqs = h.exchange_start()
 
     def launch_one(i, kt):
-        ghosts, nrms, face_cb = h.ghost_args(i)
-        xf = xs[i] if xs else outs[i]
-        ext.dslash_wilson(
-            outs[i].data, norm_or_empty(outs[i]), inps[i].data,
-            norm_or_empty(inps[i]), gauge.data, cl_t, xf.data,
-            norm_or_empty(xf), list(geo.dims), geo.parity_offset,
-            geo.volume_cb, parity, bool(dagger), mode, xpay, float(a),
-            RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb,
-            mask, kt, 0.0, 0.0)
+        _launch_wilson(ext, outs[i], inps[i], gauge, cl_t,
+                       xs[i] if xs else None, parity, dagger, mode, a,
+                       h.ghost_args(i) + (mask,), kt)
 
     # interiors overlap the batched transfer: mrhs kernels offset into
     # the batch ghost slabs from the group's base slice
     for r0, g in groups:
-        ghosts, nrms, face_cb = h.ghost_args(r0)
-        launch_group(r0, g, 2, ghosts, nrms, face_cb)
+        launch_group(r0, g, 2, h.ghost_args(r0) + (mask,))
     for i in range(rem0, n):
         launch_one(i, 2)
     for r in reqs:
@@ -521,12 +553,8 @@ def _dslash_batch_oracle(outs, inps, gauge, parity, dagger, a, xs,
     exchange_tensors(sends, recvs)
     u = gauge.to_complex()
     for i in range(n):
-        halo = {
-            "mask": mask,
-            "psi": {k: v[i] for k, v in recvs.items()},
-            "u_bwd": {mu: gauge.bwd_ghost(mu, parity)
-                      for mu in active_dims(mask)},
-        }
+        halo = _oracle_halo(gauge, parity, mask,
+                            {k: v[i] for k, v in recvs.items()})
         res = ref.dslash_wilson_parity(u, psis[i], geo, parity, dagger,
                                        halo=halo)
         if mode == CLOV_POST:
@@ -610,7 +638,7 @@ def dslash_staggered(out: SpinorField, inp: SpinorField, gauge: GaugeField,
         ext = hip_ext()
         xf = x if x is not None else out
         lng = (long_gauge.data if long_gauge is not None
-               else torch.empty(0, dtype=out.data.dtype, device=out.device))
+               else empty_tensor(out.data.dtype, out.device))
 
         def launch(kt, ghosts=[], nrms=[], face_cb=[]):
             ext.dslash_staggered(
@@ -643,13 +671,9 @@ def dslash_staggered(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     psi = inp.to_complex()[0]
     halo = None
     if mask:
-        from ..parallel.halo import active_dims, exchange_psi_oracle
-        halo = {
-            "mask": mask,
-            "psi": exchange_psi_oracle(psi, geo, 1 - parity, mask),
-            "u_bwd": {mu: gauge.bwd_ghost(mu, parity)
-                      for mu in active_dims(mask)},
-        }
+        from ..parallel.halo import exchange_psi_oracle
+        halo = _oracle_halo(gauge, parity, mask,
+                            exchange_psi_oracle(psi, geo, 1 - parity, mask))
     res = ref.dslash_staggered_parity(u, psi, geo, parity, halo=halo)
     if long_gauge is not None:
         halo3 = None
@@ -687,15 +711,18 @@ def dwf5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
                  xpay, bool(dagger), float(a), float(alpha), float(beta),
                  float(mf), kind)
         return out
-    psi = inp.to_complex()[0]
-    if kind == 0:
-        res = ref.dslash5(psi, Ls, alpha, beta, mf, dagger)
-        if xpay:
-            res = a * x.to_complex()[0] + res
-    else:
-        res = a * ref.m5inv(psi, Ls, alpha, beta, mf, dagger)
-        if xpay:
-            res = x.to_complex()[0] + res
+    op5 = ref.dslash5 if kind == 0 else ref.m5inv
+    return _finish5(out, op5(inp.to_complex()[0], Ls, alpha, beta, mf, dagger),
+                    kind, a, x)
+
+
+def _finish5(out: SpinorField, res, kind: int, a, x: Optional[SpinorField]):
+    """CPU tail of the 5th-dimension ops, res = the bare operator on `in`:
+    kind=0: out = [a*x +] res;  kind=1: out = [x +] a * res."""
+    if kind != 0:
+        res = a * res
+    if x is not None:
+        res = (a * x.to_complex()[0] if kind == 0 else x.to_complex()[0]) + res
     out.from_complex(res.unsqueeze(0))
     return out
 
@@ -782,17 +809,9 @@ def zdwf5_op(out: SpinorField, inp: SpinorField, diag, hop, mf: float,
                   t["el"], t["cwu_re"], t["cwu_im"], t["cwl_re"],
                   t["cwl_im"])
         return out
-    psi = inp.to_complex()[0]
-    if kind == 0:
-        res = ref.zdslash5(psi, Ls, diag, hop, mf, dagger)
-        if xpay:
-            res = a * x.to_complex()[0] + res
-    else:
-        res = a * ref.zm5inv(psi, Ls, diag, hop, mf, dagger)
-        if xpay:
-            res = x.to_complex()[0] + res
-    out.from_complex(res.unsqueeze(0))
-    return out
+    op5 = ref.zdslash5 if kind == 0 else ref.zm5inv
+    return _finish5(out, op5(inp.to_complex()[0], Ls, diag, hop, mf, dagger),
+                    kind, a, x)
 
 
 def eofa5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
@@ -831,18 +850,9 @@ def eofa5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
                   bool(dagger), float(a), float(alpha), float(beta),
                   float(mf), uu, ww, float(sh_k), int(pm), kind)
         return out
-    psi = inp.to_complex()[0]
-    if kind == 0:
-        res = ref.m5_eofa(psi, Ls, alpha, beta, mf, sh, pm, u, w, dagger)
-        if xpay:
-            res = a * x.to_complex()[0] + res
-    else:
-        res = a * ref.m5inv_eofa(psi, Ls, alpha, beta, mf, sh, pm, u, w,
-                                 dagger)
-        if xpay:
-            res = x.to_complex()[0] + res
-    out.from_complex(res.unsqueeze(0))
-    return out
+    op5 = ref.m5_eofa if kind == 0 else ref.m5inv_eofa
+    return _finish5(out, op5(inp.to_complex()[0], Ls, alpha, beta, mf, sh, pm,
+                             u, w, dagger), kind, a, x)
 
 
 def dwf_halo_exchange(inp: SpinorField, parity_in: int, dagger: bool):
@@ -854,14 +864,30 @@ def dwf_halo_exchange(inp: SpinorField, parity_in: int, dagger: bool):
     if not mask:
         return None
     if on_gpu(inp):
-        from ..parallel.halo import get_dwf_halo
-        h = get_dwf_halo(inp.geo, inp.precision, inp.device, mask, inp.ls)
-        h.pack_exchange(hip_ext(), inp, parity_in, bool(dagger))
+        from ..parallel.halo import get_spinor_halo
+        h = get_spinor_halo(inp.geo, inp.precision, inp.device, mask,
+                            n_slab=inp.ls)
+        Vcb = inp.geo.volume_cb
+        for s in range(inp.ls):  # every slice into its slab: ONE exchange
+            h.pack(hip_ext(), inp, parity_in, bool(dagger), slab=s,
+                   v_stride=inp.ls * Vcb, s_offset=s * Vcb)
+        h.exchange()
         return ("native", mask, h)
     from ..parallel.halo import exchange_psi5_oracle
     ghosts = exchange_psi5_oracle(inp.to_complex()[0], inp.geo, parity_in,
                                   mask, inp.ls)
     return ("oracle", mask, ghosts)
+
+
+def _slab_halo(halo, mask: int, s: int):
+    """(halo, kt) launch arguments of slice s from what dwf_halo_exchange
+    returned: the fused ghost-aware kernel (the exchange is already done),
+    or the local one when no dim is partitioned."""
+    if not mask:
+        return _NO_HALO, 0
+    kind, hmask, h = halo
+    assert kind == "native" and hmask == mask
+    return h.ghost_args(s) + (mask,), 1
 
 
 def dslash_wilson_slices(out: SpinorField, inp: SpinorField,
@@ -882,26 +908,13 @@ def dslash_wilson_slices(out: SpinorField, inp: SpinorField,
     groups, rem0 = _mrhs_groups(Ls) if gpu else ([], 0)
     if gpu and groups:
         ext = hip_ext()
-        xpay = x is not None
-        xf = x if x is not None else out
-        cl_t = torch.empty(0, dtype=out.data.dtype, device=out.device)
+        cl_t = empty_tensor(out.data.dtype, out.device)
         for s0, gsz in groups:
-            ghosts, nrms, face_cb, kt = [], [], [], 0
-            if mask:
-                kind, hmask, h = halo
-                assert kind == "native" and hmask == mask
-                ghosts, nrms, face_cb = h.ghost_args(s0)
-                kt = 1
-            ext.dslash_wilson_mrhs(
-                [out.data] * gsz, [norm_or_empty(out)] * gsz,
-                [inp.data] * gsz, [norm_or_empty(inp)] * gsz,
-                gauge.data, cl_t, [xf.data] * gsz if xpay else [],
-                [norm_or_empty(xf)] * gsz if xpay else [],
-                list(geo.dims), geo.parity_offset, Vcb, parity,
-                bool(dagger), PLAIN, xpay, float(a),
-                RECON_COMPS[gauge.reconstruct], ghosts, nrms, face_cb,
-                mask, kt, inp.volume_cb,
-                [(s0 + r) * Vcb for r in range(gsz)])
+            _launch_wilson_mrhs(
+                ext, [out] * gsz, [inp] * gsz, gauge, cl_t,
+                [x] * gsz if x is not None else [], parity, dagger, PLAIN, a,
+                *_slab_halo(halo, mask, s0), v_stride=inp.volume_cb,
+                s_offsets=[(s0 + r) * Vcb for r in range(gsz)])
     for s in range(rem0, Ls):
         dslash_wilson_slice(out, inp, gauge, parity, s, dagger, a=a, x=x,
                             halo=halo)
@@ -996,21 +1009,10 @@ def dslash_wilson_slice(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     xpay = x is not None
     Vcb = geo.volume_cb
     if on_gpu(out, inp):
-        ext = hip_ext()
-        xf = x if x is not None else out
-        cl_t = torch.empty(0, dtype=out.data.dtype, device=out.device)
-        ghosts, nrms, face_cb, kt = [], [], [], 0
-        if mask:
-            kind, hmask, h = halo
-            assert kind == "native" and hmask == mask
-            ghosts, nrms, face_cb = h.ghost_args(s)
-            kt = 1  # fused ghost-aware kernel (exchange already done)
-        ext.dslash_wilson(
-            out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
-            gauge.data, cl_t, xf.data, norm_or_empty(xf),
-            list(geo.dims), geo.parity_offset, Vcb, parity, bool(dagger),
-            PLAIN, xpay, float(a), RECON_COMPS[gauge.reconstruct], ghosts,
-            nrms, face_cb, mask, kt, 0.0, 0.0, inp.volume_cb, s * Vcb)
+        _launch_wilson(hip_ext(), out, inp, gauge,
+                       empty_tensor(out.data.dtype, out.device), x, parity,
+                       dagger, PLAIN, a, *_slab_halo(halo, mask, s),
+                       v_stride=inp.volume_cb, s_offset=s * Vcb)
         return out
     u = gauge.to_complex()
     sl = slice(s * Vcb, (s + 1) * Vcb)
@@ -1019,13 +1021,8 @@ def dslash_wilson_slice(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     if mask:
         kind, hmask, ghosts5 = halo
         assert kind == "oracle" and hmask == mask
-        from ..parallel.halo import active_dims
-        oh = {
-            "mask": mask,
-            "psi": {k: v[s] for k, v in ghosts5.items()},
-            "u_bwd": {mu: gauge.bwd_ghost(mu, parity)
-                      for mu in active_dims(mask)},
-        }
+        oh = _oracle_halo(gauge, parity, mask,
+                          {k: v[s] for k, v in ghosts5.items()})
     res = ref.dslash_wilson_parity(u, psi, geo, parity, dagger, halo=oh)
     if xpay:
         res = x.to_complex()[0][sl] + a * res

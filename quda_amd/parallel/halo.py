@@ -112,62 +112,98 @@ def ghost_width(ncomp: int, precision: str) -> int:
 
 class SpinorHalo:
     """Persistent send/recv ghost buffers for one (geometry, precision,
-    device, mask, ncomp) signature (role of the reference's static ghost
-    arenas, lattice_field.h:250). ncomp = 12 (spin-projected Wilson) or
-    6 (staggered full site)."""
+    device, mask, ncomp, depth, n_slab) signature (role of the reference's
+    static ghost arenas, lattice_field.h:250). ncomp = 12 (spin-projected
+    Wilson) or 6 (staggered full site); depth = ghost layers (3 for the
+    staggered Naik term).
+
+    Per (mu, dir) one contiguous tensor [ncomp/gw, depth*Fcb, gw], norms
+    [depth*Fcb]. With n_slab (the Ls slices of a 5-d field, or the sides of
+    a multi-RHS batch) both gain a leading slab dimension: every slab packs
+    into its own slice and the whole buffer still ships as ONE message per
+    (mu, dir) (ref: create_comms_batch, dslash_wilson.hpp:48). The multi-RHS
+    kernels offset into the slab from the slice they are handed
+    (csrc/halo.h load_r), so this layout is load-bearing."""
 
     def __init__(self, geo: LatticeGeometry, precision: str, device,
-                 mask: int, ncomp: int = 12, depth: int = 1):
+                 mask: int, ncomp: int = 12, depth: int = 1,
+                 n_slab: Optional[int] = None):
         from ..fields.layout import DTYPE_OF
         self.geo = geo
         self.precision = precision
         self.mask = mask
         self.ncomp = ncomp
-        self.depth = depth  # ghost layers (3 for the staggered Naik term)
+        self.depth = depth
+        self.n_slab = n_slab
         self.device = torch.device(device)
+        self.dtype = DTYPE_OF[precision]
         self.send: Dict[Key, torch.Tensor] = {}
         self.recv: Dict[Key, torch.Tensor] = {}
         self.send_nrm: Dict[Key, torch.Tensor] = {}
         self.recv_nrm: Dict[Key, torch.Tensor] = {}
         gw = ghost_width(ncomp, precision)
-        dt = DTYPE_OF[precision]
+        lead = () if n_slab is None else (n_slab,)
         for mu in active_dims(mask):
             fcb = geo.face_volume_cb(mu) * depth
-            for d in (0, 1):
-                shape = (ncomp // gw, fcb, gw)
-                self.send[(mu, d)] = torch.empty(shape, dtype=dt, device=device)
-                self.recv[(mu, d)] = torch.empty(shape, dtype=dt, device=device)
-                if precision in ("half", "quarter"):
-                    self.send_nrm[(mu, d)] = torch.empty(fcb, dtype=torch.float32,
-                                                         device=device)
-                    self.recv_nrm[(mu, d)] = torch.empty(fcb, dtype=torch.float32,
-                                                         device=device)
+            for key in ((mu, 0), (mu, 1)):
+                for bufs, nrms in ((self.send, self.send_nrm),
+                                   (self.recv, self.recv_nrm)):
+                    bufs[key] = torch.empty(lead + (ncomp // gw, fcb, gw),
+                                            dtype=self.dtype, device=device)
+                    if precision in ("half", "quarter"):
+                        nrms[key] = torch.empty(lead + (fcb,),
+                                                dtype=torch.float32,
+                                                device=device)
 
-    def pack(self, ext, inp, parity: int, dagger: bool) -> None:
-        """Pack all active faces of `inp` (the dslash input, at `parity`):
-        Wilson ghosts carry the projector the consuming hop applies,
-        staggered ghosts the full site."""
-        geo = self.geo
-        empty = torch.empty(0, dtype=torch.float32, device=self.device)
-        from ..ops.dispatch import norm_or_empty
+    def faces(self, dagger: bool):
+        """(key, s01, edge, fcb) of every face to pack: send[(mu, d)] is the
+        x_mu = 0 (d = 0) or X-1 (d = 1) face, with the projector sign the
+        consuming hop applies."""
         for mu in active_dims(self.mask):
-            fcb = geo.face_volume_cb(mu)
+            fcb = self.geo.face_volume_cb(mu)
             for d in (0, 1):
-                edge = 0 if d == 0 else 1
-                if self.ncomp == 6:
-                    ext.pack_face_stag(self.send[(mu, d)],
-                                       self.send_nrm.get((mu, d), empty),
-                                       inp.data, norm_or_empty(inp),
-                                       list(geo.dims), geo.parity_offset,
-                                       geo.volume_cb, parity, mu, edge, fcb,
-                                       self.depth)
-                else:
-                    s01 = d ^ (1 if dagger else 0)
-                    ext.pack_face(self.send[(mu, d)],
-                                  self.send_nrm.get((mu, d), empty),
-                                  inp.data, norm_or_empty(inp),
-                                  list(geo.dims), geo.parity_offset,
-                                  geo.volume_cb, parity, mu, s01, edge, fcb)
+                yield (mu, d), d ^ (1 if dagger else 0), d, fcb
+
+    def _pack_face(self, ext, dst, dst_nrm, inp, parity: int, mu: int,
+                   s01: int, edge: int, fcb: int, v_stride: int,
+                   s_offset: int) -> None:
+        from ..ops.dispatch import norm_or_empty
+        geo = self.geo
+        if self.ncomp == 6:  # staggered ghosts carry the full site
+            ext.pack_face_stag(dst, dst_nrm, inp.data, norm_or_empty(inp),
+                               list(geo.dims), geo.parity_offset,
+                               geo.volume_cb, parity, mu, edge, fcb,
+                               self.depth)
+        else:
+            ext.pack_face(dst, dst_nrm, inp.data, norm_or_empty(inp),
+                          list(geo.dims), geo.parity_offset, geo.volume_cb,
+                          parity, mu, s01, edge, fcb, v_stride=v_stride,
+                          s_offset=s_offset)
+
+    def _slot(self, bufs, nrms, key: Key, slab: Optional[int]):
+        """(buffer, norm) of one face, or of one slab of it."""
+        from ..ops.dispatch import empty_tensor
+        b, n = bufs.get(key), nrms.get(key)
+        if b is None:  # dim not partitioned
+            b = empty_tensor(self.dtype, self.device)
+        elif slab is not None:
+            b = b[slab]
+        if n is None:  # no norms at this precision, or dim not partitioned
+            n = empty_tensor(torch.float32, self.device)
+        elif slab is not None:
+            n = n[slab]
+        return b, n
+
+    def pack(self, ext, inp, parity: int, dagger: bool,
+             slab: Optional[int] = None, v_stride: int = 0,
+             s_offset: int = 0) -> None:
+        """Pack all active faces of `inp` (the dslash input, at `parity`)
+        into the send buffers, or into their slice `slab`. v_stride /
+        s_offset address one 4-d slice of a 5-d input."""
+        for key, s01, edge, fcb in self.faces(dagger):
+            dst, dst_nrm = self._slot(self.send, self.send_nrm, key, slab)
+            self._pack_face(ext, dst, dst_nrm, inp, parity, key[0], s01, edge,
+                            fcb, v_stride, s_offset)
 
     def exchange(self) -> None:
         for r in self.exchange_start():
@@ -175,36 +211,32 @@ class SpinorHalo:
 
     def exchange_start(self) -> list:
         reqs = exchange_tensors_start(self.send, self.recv)
-        if self.precision in ("half", "quarter"):
+        if self.recv_nrm:
             reqs += exchange_tensors_start(self.send_nrm, self.recv_nrm)
         return reqs
 
-    def ghost_args(self):
-        """(ghost[8], ghost_nrm[8], face_cb[4]) lists for ext.dslash_*."""
-        empty = torch.empty(0, dtype=self.recv[next(iter(self.recv))].dtype,
-                            device=self.device) if self.recv else None
-        empty_n = torch.empty(0, dtype=torch.float32, device=self.device)
-        ghosts, nrms = [], []
-        for mu in range(4):
-            for d in (0, 1):
-                g = self.recv.get((mu, d))
-                ghosts.append(g if g is not None else empty)
-                n = self.recv_nrm.get((mu, d))
-                nrms.append(n if n is not None else empty_n)
+    def ghost_args(self, slab: Optional[int] = None):
+        """(ghost[8], ghost_nrm[8], face_cb[4]) lists for ext.dslash_*: the
+        recv buffers, or their slice `slab`."""
+        slots = [self._slot(self.recv, self.recv_nrm, (mu, d), slab)
+                 for mu in range(4) for d in (0, 1)]
         face_cb = [self.geo.face_volume_cb(mu) for mu in range(4)]
-        return ghosts, nrms, face_cb
+        return [b for b, _ in slots], [n for _, n in slots], face_cb
 
 
 _HALO_CACHE: Dict[tuple, SpinorHalo] = {}
 
 
 def get_spinor_halo(geo: LatticeGeometry, precision: str, device,
-                    mask: int, ncomp: int = 12, depth: int = 1) -> SpinorHalo:
+                    mask: int, ncomp: int = 12, depth: int = 1,
+                    n_slab: Optional[int] = None) -> SpinorHalo:
+    """The cached halo of this signature; the key holds everything the
+    object depends on (the pack reads geo.dims and geo.parity_offset)."""
     key = (geo.dims, geo.parity_offset, precision, str(device), mask, ncomp,
-           depth)
+           depth, n_slab)
     h = _HALO_CACHE.get(key)
     if h is None:
-        h = SpinorHalo(geo, precision, device, mask, ncomp, depth)
+        h = SpinorHalo(geo, precision, device, mask, ncomp, depth, n_slab)
         _HALO_CACHE[key] = h
     return h
 
@@ -236,98 +268,6 @@ def exchange_psi_oracle(psi: torch.Tensor, geo: LatticeGeometry,
     if depth == 1:
         recvs = {k: v[0] for k, v in recvs.items()}
     return recvs
-
-
-# ---------------------------------------------------------------------------
-# 5-d (domain-wall) halo: per-slice packs into one slab buffer, ONE exchange
-# ---------------------------------------------------------------------------
-
-class DwfHalo:
-    """Ghost buffers for 5-d fields: one slab per (mu,dir) shaped
-    [Ls, 12/gw, Fcb, gw]; each s-slice packs into its slab and the whole
-    buffer ships in a single message per (mu,dir)."""
-
-    def __init__(self, geo: LatticeGeometry, precision: str, device,
-                 mask: int, ls: int):
-        from ..fields.layout import DTYPE_OF
-        self.geo = geo
-        self.precision = precision
-        self.mask = mask
-        self.ls = ls
-        self.device = torch.device(device)
-        gw = ghost_width(12, precision)
-        dt = DTYPE_OF[precision]
-        self.send, self.recv = {}, {}
-        self.send_nrm, self.recv_nrm = {}, {}
-        for mu in active_dims(mask):
-            fcb = geo.face_volume_cb(mu)
-            for d in (0, 1):
-                shape = (ls, 12 // gw, fcb, gw)
-                self.send[(mu, d)] = torch.empty(shape, dtype=dt, device=device)
-                self.recv[(mu, d)] = torch.empty(shape, dtype=dt, device=device)
-                if precision in ("half", "quarter"):
-                    self.send_nrm[(mu, d)] = torch.empty((ls, fcb),
-                                                         dtype=torch.float32,
-                                                         device=device)
-                    self.recv_nrm[(mu, d)] = torch.empty((ls, fcb),
-                                                         dtype=torch.float32,
-                                                         device=device)
-
-    def pack_exchange(self, ext, inp, parity: int, dagger: bool) -> None:
-        geo = self.geo
-        Vcb = geo.volume_cb
-        empty = torch.empty(0, dtype=torch.float32, device=self.device)
-        for mu in active_dims(self.mask):
-            fcb = geo.face_volume_cb(mu)
-            for d in (0, 1):
-                s01 = d ^ (1 if dagger else 0)
-                edge = 0 if d == 0 else 1
-                for s in range(self.ls):
-                    nrm = (self.send_nrm[(mu, d)][s]
-                           if self.precision in ("half", "quarter") else empty)
-                    ext.pack_face(self.send[(mu, d)][s], nrm,
-                                  inp.data, _norm_or_empty(inp),
-                                  list(geo.dims), geo.parity_offset, Vcb,
-                                  parity, mu, s01, edge, fcb,
-                                  v_stride=self.ls * Vcb, s_offset=s * Vcb)
-        exchange_tensors(self.send, self.recv)
-        if self.precision in ("half", "quarter"):
-            exchange_tensors(self.send_nrm, self.recv_nrm)
-
-    def ghost_args(self, s: int):
-        empty_n = torch.empty(0, dtype=torch.float32, device=self.device)
-        ghosts, nrms = [], []
-        for mu in range(4):
-            for d in (0, 1):
-                g = self.recv.get((mu, d))
-                if g is None:
-                    ghosts.append(torch.empty(0, dtype=next(iter(self.recv.values())).dtype,
-                                              device=self.device))
-                    nrms.append(empty_n)
-                else:
-                    ghosts.append(g[s])
-                    nrms.append(self.recv_nrm[(mu, d)][s]
-                                if self.precision in ("half", "quarter") else empty_n)
-        face_cb = [self.geo.face_volume_cb(mu) for mu in range(4)]
-        return ghosts, nrms, face_cb
-
-
-def _norm_or_empty(f):
-    from ..ops.dispatch import norm_or_empty
-    return norm_or_empty(f)
-
-
-_DWF_HALO_CACHE: Dict[tuple, DwfHalo] = {}
-
-
-def get_dwf_halo(geo: LatticeGeometry, precision: str, device, mask: int,
-                 ls: int) -> DwfHalo:
-    key = (geo.dims, precision, str(device), mask, ls)
-    h = _DWF_HALO_CACHE.get(key)
-    if h is None:
-        h = DwfHalo(geo, precision, device, mask, ls)
-        _DWF_HALO_CACHE[key] = h
-    return h
 
 
 def exchange_psi5_oracle(psi5: torch.Tensor, geo: LatticeGeometry,
@@ -389,94 +329,3 @@ def _face_lex(geo: LatticeGeometry, mu: int, edge: int) -> torch.Tensor:
         c = geo.coords[:, mu]
         cache[key] = (c == edge).nonzero(as_tuple=True)[0].contiguous()
     return cache[key]
-
-
-class BatchSpinorHalo:
-    """Multi-RHS ghost buffers: per (mu,dir) ONE contiguous tensor
-    [n_rhs, ncomp/gw, depth*Fcb, gw] so the whole batch ships as a single
-    message per face (ref: dslash create_comms_batch, the merged-halo
-    multi-RHS path — the per-RHS kernels then consume their slice)."""
-
-    def __init__(self, geo: LatticeGeometry, precision: str, device,
-                 mask: int, n_rhs: int, ncomp: int = 12):
-        from ..fields.layout import DTYPE_OF
-        self.geo = geo
-        self.precision = precision
-        self.mask = mask
-        self.n_rhs = n_rhs
-        self.ncomp = ncomp
-        self.device = torch.device(device)
-        gw = ghost_width(ncomp, precision)
-        dt = DTYPE_OF[precision]
-        self.send, self.recv = {}, {}
-        self.send_nrm, self.recv_nrm = {}, {}
-        for mu in active_dims(mask):
-            fcb = geo.face_volume_cb(mu)
-            for d in (0, 1):
-                shape = (n_rhs, ncomp // gw, fcb, gw)
-                self.send[(mu, d)] = torch.empty(shape, dtype=dt,
-                                                 device=device)
-                self.recv[(mu, d)] = torch.empty(shape, dtype=dt,
-                                                 device=device)
-                if precision in ("half", "quarter"):
-                    self.send_nrm[(mu, d)] = torch.empty(
-                        (n_rhs, fcb), dtype=torch.float32, device=device)
-                    self.recv_nrm[(mu, d)] = torch.empty(
-                        (n_rhs, fcb), dtype=torch.float32, device=device)
-
-    def pack_one(self, ext, i: int, inp, parity: int, dagger: bool) -> None:
-        geo = self.geo
-        empty = torch.empty(0, dtype=torch.float32, device=self.device)
-        from ..ops.dispatch import norm_or_empty
-        for mu in active_dims(self.mask):
-            fcb = geo.face_volume_cb(mu)
-            for d in (0, 1):
-                s01 = d ^ (1 if dagger else 0)
-                nrm = self.send_nrm.get((mu, d))
-                ext.pack_face(self.send[(mu, d)][i],
-                              nrm[i] if nrm is not None else empty,
-                              inp.data, norm_or_empty(inp),
-                              list(geo.dims), geo.parity_offset,
-                              geo.volume_cb, parity, mu, s01, d, fcb)
-
-    def exchange(self) -> None:
-        reqs = exchange_tensors_start(self.send, self.recv)
-        if self.precision in ("half", "quarter"):
-            reqs += exchange_tensors_start(self.send_nrm, self.recv_nrm)
-        for r in reqs:
-            r.wait()
-
-    def exchange_start(self) -> list:
-        reqs = exchange_tensors_start(self.send, self.recv)
-        if self.precision in ("half", "quarter"):
-            reqs += exchange_tensors_start(self.send_nrm, self.recv_nrm)
-        return reqs
-
-    def ghost_args(self, i: int):
-        """Per-RHS (ghost[8], ghost_nrm[8], face_cb[4]) slice views."""
-        empty = torch.empty(0, dtype=next(iter(self.recv.values())).dtype,
-                            device=self.device) if self.recv else None
-        empty_n = torch.empty(0, dtype=torch.float32, device=self.device)
-        ghosts, nrms = [], []
-        for mu in range(4):
-            for d in (0, 1):
-                g = self.recv.get((mu, d))
-                ghosts.append(g[i] if g is not None else empty)
-                n = self.recv_nrm.get((mu, d))
-                nrms.append(n[i] if n is not None else empty_n)
-        face_cb = [self.geo.face_volume_cb(mu) for mu in range(4)]
-        return ghosts, nrms, face_cb
-
-
-_BATCH_HALO_CACHE: Dict[tuple, "BatchSpinorHalo"] = {}
-
-
-def get_batch_halo(geo: LatticeGeometry, precision: str, device, mask: int,
-                   n_rhs: int, ncomp: int = 12) -> BatchSpinorHalo:
-    key = (geo.dims, geo.parity_offset, precision, str(device), mask,
-           n_rhs, ncomp)
-    h = _BATCH_HALO_CACHE.get(key)
-    if h is None:
-        h = BatchSpinorHalo(geo, precision, device, mask, n_rhs, ncomp)
-        _BATCH_HALO_CACHE[key] = h
-    return h

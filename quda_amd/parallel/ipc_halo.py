@@ -86,27 +86,21 @@ class IpcSpinorHalo(SpinorHalo):
 
     def pack_remote(self, ext, inp, parity: int, dagger: bool) -> None:
         """Pack every active face straight into its consumer's memory."""
-        geo = self.geo
         from ..ops.dispatch import norm_or_empty
-        empty = torch.empty(0, dtype=torch.float32, device=self.device)
-        for mu in active_dims(self.mask):
-            fcb = geo.face_volume_cb(mu)
-            for d in (0, 1):
-                edge = 0 if d == 0 else 1
-                s01 = d ^ (1 if dagger else 0)
-                if self.self_wrap[(mu, d)]:
-                    dst = self.recv[(mu, 1 - d)]
-                    dn = self.recv_nrm.get((mu, 1 - d), empty)
-                    ext.pack_face(dst, dn, inp.data, norm_or_empty(inp),
+        geo = self.geo
+        for (mu, d), s01, edge, fcb in self.faces(dagger):
+            if self.self_wrap[(mu, d)]:
+                dst, dn = self._slot(self.recv, self.recv_nrm, (mu, 1 - d),
+                                     None)
+                self._pack_face(ext, dst, dn, inp, parity, mu, s01, edge, fcb,
+                                0, 0)
+            else:
+                ext.pack_face_ptr(self.peer_ptr[(mu, d)],
+                                  self.peer_nrm_ptr.get((mu, d), 0),
+                                  inp.data, norm_or_empty(inp),
                                   list(geo.dims), geo.parity_offset,
-                                  geo.volume_cb, parity, mu, s01, edge, fcb)
-                else:
-                    pn = self.peer_nrm_ptr.get((mu, d), 0)
-                    ext.pack_face_ptr(self.peer_ptr[(mu, d)], pn,
-                                      inp.data, norm_or_empty(inp),
-                                      list(geo.dims), geo.parity_offset,
-                                      geo.volume_cb, parity, mu, s01, edge,
-                                      fcb, 0, 0)
+                                  geo.volume_cb, parity, mu, s01, edge, fcb,
+                                  0, 0)
 
     def complete(self) -> None:
         """All remote writes landed everywhere (drain + barrier)."""
@@ -120,7 +114,7 @@ _IPC_CACHE: Dict[tuple, IpcSpinorHalo] = {}
 
 def get_ipc_halo(geo, precision: str, device, mask: int,
                  ncomp: int = 12) -> IpcSpinorHalo:
-    key = (geo.dims, precision, str(device), mask, ncomp,
+    key = (geo.dims, geo.parity_offset, precision, str(device), mask, ncomp,
            comms.grid_dims(), comms.grid_coords())
     h = _IPC_CACHE.get(key)
     if h is None:

@@ -294,6 +294,7 @@ def test_dslash_mrhs_vs_per_rhs(setup, prec, nrhs):
     """k_dslash_wilson_mrhs (NRHS sides per gauge load) must match the
     per-RHS kernel bit-for-bit in PLAIN and CLOV_POST(+xpay) modes."""
     from quda_amd.fields.clover import pack_clover
+    from quda_amd.ops import dispatch
     from quda_amd.ops.dispatch import dslash_wilson_batch
     geo, g, psi, chi, A = setup
     recon = 12 if prec != "double" else 18
@@ -317,20 +318,28 @@ def test_dslash_mrhs_vs_per_rhs(setup, prec, nrhs):
     # differently per kernel); require agreement at the precision's
     # roundoff, not bitwise.
     rtol = {"half": 2e-3, "single": 1e-5, "double": 1e-13}[prec]
-    for mode, use_x, use_cl in [(PLAIN, False, None), (PLAIN, True, None),
-                                (CLOV_POST, True, cl)]:
-        for dag in (False, True):
-            dslash_wilson_batch(outs_m, inps, gd, 0, dagger=dag, a=-0.3,
-                                xs=xs if use_x else None, mode=mode,
-                                clover=use_cl)
-            for r in range(nrhs):
-                dslash_wilson(outs_1[r], inps[r], gd, 0, dagger=dag,
-                              a=-0.3, x=xs[r] if use_x else None,
-                              mode=mode, clover=use_cl)
-                ref_c = outs_1[r].to_complex()
-                dm = (outs_m[r].to_complex() - ref_c)
-                err = dm.abs().max().item() / ref_c.abs().max().item()
-                assert err < rtol, (prec, nrhs, mode, use_x, dag, r, err)
+    # the group size defaults to 1 (per-RHS launches): switch the multi-RHS
+    # kernel on, or the batch would be compared with itself
+    saved = dispatch._MRHS_GROUP
+    try:
+        dispatch._MRHS_GROUP = nrhs
+        assert dispatch._mrhs_groups(nrhs)[0]
+        for mode, use_x, use_cl in [(PLAIN, False, None), (PLAIN, True, None),
+                                    (CLOV_POST, True, cl)]:
+            for dag in (False, True):
+                dslash_wilson_batch(outs_m, inps, gd, 0, dagger=dag, a=-0.3,
+                                    xs=xs if use_x else None, mode=mode,
+                                    clover=use_cl)
+                for r in range(nrhs):
+                    dslash_wilson(outs_1[r], inps[r], gd, 0, dagger=dag,
+                                  a=-0.3, x=xs[r] if use_x else None,
+                                  mode=mode, clover=use_cl)
+                    ref_c = outs_1[r].to_complex()
+                    dm = (outs_m[r].to_complex() - ref_c)
+                    err = dm.abs().max().item() / ref_c.abs().max().item()
+                    assert err < rtol, (prec, nrhs, mode, use_x, dag, r, err)
+    finally:
+        dispatch._MRHS_GROUP = saved
 
 
 @pytest.mark.parametrize("prec", ["half", "single"])
