@@ -35,6 +35,7 @@ KERNEL_SOURCES = [
     "dslash_wilson_mrhs.hip",
     "coarse.hip",
     "heatbath.hip",
+    "gauge_path.hip",
     "transfer.hip",
     "galerkin.hip",
 ]

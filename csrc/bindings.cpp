@@ -756,6 +756,99 @@ static void flow_expmul_dir(at::Tensor out, at::Tensor in, at::Tensor Zc,
   check_launch("expmul");
 }
 
+// shape checks shared by the two path-table entries: a periodic single-rank
+// lattice of even extents whose volume matches the gauge tensor
+static void check_path_lattice(const char *what, const at::Tensor &u,
+                               const std::vector<int64_t> &dims, int64_t Vcb) {
+  TORCH_CHECK(u.is_cuda() && u.is_contiguous() &&
+                  u.scalar_type() == at::kComplexDouble,
+              what, ": u must be a contiguous complex128 GPU tensor");
+  TORCH_CHECK(dims.size() == 4, what, ": dims must hold the 4 extents");
+  int64_t vol = 1;
+  for (int k = 0; k < 4; ++k) {
+    TORCH_CHECK(dims[k] >= 2 && dims[k] % 2 == 0, what,
+                ": extents must be even and >= 2");
+    vol *= dims[k];
+  }
+  TORCH_CHECK(Vcb > 0 && vol == 2 * Vcb && vol < (1LL << 31), what,
+              ": Vcb does not match dims");
+  TORCH_CHECK(u.numel() == 4 * 2 * Vcb * 9, what, ": u is not [4,2,Vcb,3,3]");
+}
+
+static void gauge_path_dir(at::Tensor out, at::Tensor u, at::Tensor steps,
+                           at::Tensor lens, at::Tensor coefs,
+                           std::vector<int64_t> dims, int64_t parity_offset,
+                           int64_t Vcb, int64_t mu, double scale, double dt,
+                           bool ta, bool accumulate) {
+  const char *what = "gauge_path_dir";
+  check_path_lattice(what, u, dims, Vcb);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+                  out.scalar_type() == at::kComplexDouble &&
+                  out.numel() == u.numel() && out.device() == u.device() &&
+                  out.data_ptr() != u.data_ptr(),
+              what, ": out must be a separate tensor shaped like u");
+  TORCH_CHECK(steps.is_contiguous() && steps.scalar_type() == at::kChar &&
+                  steps.dim() == 3 && steps.size(0) == 4 &&
+                  steps.size(2) == QA_PATH_STEPS &&
+                  (uintptr_t)steps.data_ptr() % 8 == 0 &&
+                  steps.device() == u.device(),
+              what, ": steps must be int8 [4][np][8] on u's device");
+  const int64_t np = steps.size(1);
+  TORCH_CHECK(np >= 1 && np <= QA_PATH_MAX, what, ": np out of range");
+  TORCH_CHECK(lens.is_contiguous() && lens.scalar_type() == at::kInt &&
+                  lens.numel() == 4 * np && lens.device() == u.device(),
+              what, ": lens must be int32 [4][np]");
+  TORCH_CHECK(coefs.is_contiguous() && coefs.scalar_type() == at::kDouble &&
+                  coefs.numel() == 4 * np && coefs.device() == u.device(),
+              what, ": coefs must be float64 [4][np]");
+  TORCH_CHECK(mu >= 0 && mu < 4, what, ": mu out of range");
+  GaugePathCall c{};
+  c.out = out.data_ptr();
+  c.u = u.data_ptr();
+  c.steps = steps.data_ptr();
+  c.lens = lens.data_ptr<int>();
+  c.coefs = coefs.data_ptr<double>();
+  c.np = (int)np;
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  c.mu = (int)mu;
+  c.scale = scale;
+  c.dt = dt;
+  c.ta = ta;
+  c.accumulate = accumulate;
+  launch_gauge_path(c, stream());
+  check_launch(what);
+}
+
+static void gauge_loop_trace(at::Tensor tr, at::Tensor u, at::Tensor steps,
+                             at::Tensor lens, std::vector<int64_t> dims,
+                             int64_t parity_offset, int64_t Vcb) {
+  const char *what = "gauge_loop_trace";
+  check_path_lattice(what, u, dims, Vcb);
+  TORCH_CHECK(steps.is_contiguous() && steps.scalar_type() == at::kChar &&
+                  steps.dim() == 2 && steps.size(1) == QA_PATH_STEPS &&
+                  (uintptr_t)steps.data_ptr() % 8 == 0 &&
+                  steps.device() == u.device(),
+              what, ": steps must be int8 [nloops][8] on u's device");
+  const int64_t nl = steps.size(0);
+  TORCH_CHECK(nl >= 1 && nl < (1 << 20), what, ": nloops out of range");
+  TORCH_CHECK(lens.is_contiguous() && lens.scalar_type() == at::kInt &&
+                  lens.numel() == nl && lens.device() == u.device(),
+              what, ": lens must be int32 [nloops]");
+  TORCH_CHECK(tr.is_cuda() && tr.is_contiguous() &&
+                  tr.scalar_type() == at::kComplexDouble &&
+                  tr.numel() == nl * 2 * Vcb && tr.device() == u.device(),
+              what, ": tr must be complex128 [nloops][2][Vcb]");
+  LoopTraceCall c{};
+  c.tr = tr.data_ptr();
+  c.u = u.data_ptr();
+  c.steps = steps.data_ptr();
+  c.lens = lens.data_ptr<int>();
+  c.nloops = (int)nl;
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  launch_loop_trace(c, stream());
+  check_launch(what);
+}
+
 static void coarse_dslash_mfma(at::Tensor mats, at::Tensor nbr9,
                                at::Tensor c, at::Tensor out, int64_t Na,
                                int64_t Nc, int64_t NR) {
@@ -987,6 +1080,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ghost_nrm"), py::arg("face_cb"), py::arg("comm_mask"),
         py::arg("kt"), py::arg("v_stride") = 0,
         py::arg("s_offsets") = std::vector<int64_t>{});
+  m.def("gauge_path_dir", &gauge_path_dir,
+        "path-table force / path product of one direction (fused mom update)");
+  m.def("gauge_loop_trace", &gauge_loop_trace,
+        "per-site traces of a table of closed loops");
   m.def("flow_zmat_dir", &flow_zmat_dir, "wilson-flow Z = eps TA[S U^d]");
   m.def("flow_expmul_dir", &flow_expmul_dir, "U' = exp(Zc) U");
   m.def("stout_smear_dir", &stout_smear_dir,

@@ -313,6 +313,37 @@ void launch_stout(const StoutCall &c, hipStream_t st);
 void launch_zmat(const StoutCall &c, hipStream_t st);    // Z = eps TA[S U^d]
 void launch_expmul(const StoutCall &c, hipStream_t st);  // U' = exp(Zc) U
 
+// path-table force / path product and loop traces (csrc/gauge_path.hip).
+// A path is QA_PATH_STEPS int8 steps +-(nu+1), zero padded and 8-byte
+// aligned; tails hold at most 7 steps, closed loops 8.
+#define QA_PATH_STEPS 8
+#define QA_PATH_MAX 64
+struct GaugePathCall {
+  void *out;            // [4][2][Vcb][3][3] complex double; only mu written
+  const void *u;        // same shape, never aliases out
+  const void *steps;    // [4][np][QA_PATH_STEPS] int8
+  const int *lens;      // [4][np]
+  const double *coefs;  // [4][np]
+  int np;               // tails per direction, <= QA_PATH_MAX
+  LatDesc lat;
+  int mu;
+  double scale;         // force: -beta/6
+  double dt;            // accumulate: out += dt * result
+  bool ta;              // project traceless-antihermitian (force)
+  bool accumulate;      // read-modify-write out (fused momentum update)
+};
+void launch_gauge_path(const GaugePathCall &c, hipStream_t st);
+
+struct LoopTraceCall {
+  void *tr;           // [nloops][2][Vcb] complex double
+  const void *u;
+  const void *steps;  // [nloops][QA_PATH_STEPS] int8
+  const int *lens;    // [nloops]
+  int nloops;
+  LatDesc lat;
+};
+void launch_loop_trace(const LoopTraceCall &c, hipStream_t st);
+
 #define QA_ZMAX 32
 
 struct ZCoef {  // host-filled complex coefficient tables (double re/im)

@@ -613,9 +613,47 @@ def perform_gauge_smear_quda(kind: str, n_steps: int, coeff: float,
 # -- HMC entry points (ref: computeGaugeForceQuda, updateGaugeFieldQuda,
 # momActionQuda, momResidentQuda) ------------------------------------------
 
-def compute_gauge_force_quda(beta: float) -> torch.Tensor:
-    from .gauge import gauge_force
-    return gauge_force(_R.u_complex, _R.geo, beta)
+def compute_gauge_force_quda(beta: float, action=None, mom=None, dt=None,
+                             native=None) -> torch.Tensor:
+    """Force of the resident field: Wilson by default, any
+    gauge.paths.LoopAction through `action`. With mom and dt the updated
+    momentum mom + dt*F is returned (in place on the native path), as the
+    reference's computeGaugeForceQuda does. `native` overrides
+    QUDA_AMD_NATIVE_GAUGE_FORCE."""
+    if action is None and mom is None:
+        from .gauge import gauge_force
+        return gauge_force(_R.u_complex, _R.geo, beta, native=native)
+    from .gauge.ops import path_gauge_force
+    from .gauge.paths import LoopAction
+    action = LoopAction.wilson() if action is None else action
+    return path_gauge_force(_R.u_complex, _R.geo, action, beta, mom=mom,
+                            dt=dt, native=native)
+
+
+def compute_gauge_path_quda(paths, coeffs, scale: float = 1.0, out=None,
+                            native=None) -> torch.Tensor:
+    """ref: computeGaugePathQuda — out_mu(x) (+)= scale * U_mu(x) *
+    sum_p coeffs[p] T_p(x+mu) with paths[mu][p] the tail of path p in
+    direction mu (the reference's input_path_buf[dim][num_paths] without
+    its leading +mu step) and coeffs shared by the four directions."""
+    from .gauge.ops import path_gauge_product
+    from .gauge.paths import ForceTable
+    assert len(paths) == 4 and all(len(pl) == len(coeffs) for pl in paths)
+    table = ForceTable([[(c, tuple(t)) for c, t in zip(coeffs, pl)]
+                        for pl in paths])
+    return path_gauge_product(_R.u_complex, _R.geo, table, scale, out=out,
+                              native=native)
+
+
+def compute_gauge_loop_trace_quda(paths, coeffs=None, factor: float = 1.0,
+                                  native=None):
+    """ref: computeGaugeLoopTraceQuda — [factor * c_i * sum_x tr P_i(x)]
+    for every closed loop i (unnormalized complex traces, global)."""
+    from .gauge.ops import loop_traces
+    coeffs = coeffs or [1.0] * len(paths)
+    traces = loop_traces(_R.u_complex, _R.geo, [tuple(p) for p in paths],
+                         native=native)
+    return [factor * c * t for c, t in zip(coeffs, traces)]
 
 
 def update_gauge_field_quda(mom: torch.Tensor, dt: float) -> None:
@@ -642,16 +680,26 @@ def mom_resident_quda(mom: Optional[torch.Tensor] = None) -> torch.Tensor:
     return _MOM["p"]
 
 
-def compute_gauge_path_force_quda(paths, coeffs, beta: float = 1.0
-                                  ) -> torch.Tensor:
+def compute_gauge_path_force_quda(paths, coeffs, beta: float = 1.0,
+                                  native=None) -> torch.Tensor:
     """ref: computeGaugeForceQuda with explicit input paths — the force
     of S = beta * sum_i c_i sum_x Re tr[1 - P_i(x)/3] for arbitrary
     signed-direction paths, by reverse-mode differentiation of the loop
     traces (validated against the analytic plaquette force and FD in
     the tests). Single-rank (autograd path); the plaquette action has
-    the analytic multi-rank force."""
+    the analytic multi-rank force. With the native gauge-force flag on
+    (native / QUDA_AMD_NATIVE_GAUGE_FORCE) and an eligible resident field
+    the path-table HIP kernel computes the same force analytically."""
     from .gauge.ops import path_product, project_ta
     from .parallel import comms
+    from .gauge.ops import _native_flag
+    if _native_flag(native):
+        from .gauge.ops import gauge_path_eligible, path_gauge_force
+        from .gauge.paths import LoopAction
+        action = LoopAction([tuple(p) for p in paths], list(coeffs))
+        if gauge_path_eligible(_R.u_complex, action, native):
+            return path_gauge_force(_R.u_complex, _R.geo, action, beta,
+                                    native=native)
     assert comms.comm_size() == 1, "autograd path force is single-rank"
     geo = _R.geo
     u_req = _R.u_complex.detach().clone().requires_grad_(True)

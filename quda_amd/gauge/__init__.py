@@ -12,7 +12,10 @@ from .ops import (ape_smear, exp_su3, gauge_action, gauge_force,
                   over_improved_stout_smear, topological_charge_density,
                   improved_gauge_action, improved_gauge_force,
                   energy_density, wilson_flow_measure, flow_scale_t0,
-                  flow_scale_w0)
+                  flow_scale_w0, path_gauge_force, path_gauge_product,
+                  loop_action, loop_traces)
+from .paths import (LoopAction, ForceTable, force_table,
+                    path_force_reference)
 from .hmc import (hmc_trajectory, leapfrog, mom_action, nested_leapfrog,
                   omelyan, random_momentum)
 from .fix import gauge_fix_ovr, gauge_fix_quality
@@ -27,7 +30,9 @@ __all__ = ["plaquette", "gauge_action", "staple_sum", "gauge_force",
            "hyp_smear", "loop_trace", "path_product", "det_trace",
            "over_improved_stout_smear", "topological_charge_density",
            "improved_gauge_action", "improved_gauge_force",
-           "flow_scale_w0",
+           "flow_scale_w0", "path_gauge_force", "path_gauge_product",
+           "loop_action", "loop_traces", "LoopAction", "ForceTable",
+           "force_table", "path_force_reference",
            "leapfrog", "hmc_trajectory", "mom_action", "random_momentum",
            "omelyan", "nested_leapfrog",
            "heatbath_sweep", "overrelax_sweep", "wilson_fermion_force",

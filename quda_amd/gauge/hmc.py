@@ -56,9 +56,15 @@ def mom_action(P: torch.Tensor) -> float:
 
 
 def leapfrog(u: torch.Tensor, P: torch.Tensor, geo: LatticeGeometry,
-             beta: float, n_steps: int, dt: float):
+             beta: float, n_steps: int, dt: float, action=None, native=None):
     """Leapfrog MD: returns evolved (u, P). Force from gauge_force
-    (pdot = F), link update U <- exp(dt P) U."""
+    (pdot = F), link update U <- exp(dt P) U. With a LoopAction `action`
+    the force is path_gauge_force of that action; where the native
+    gauge-force flag (native / QUDA_AMD_NATIVE_GAUGE_FORCE) is on and the
+    field eligible, a step is the fused force-and-momentum kernel plus the
+    expmul kernel."""
+    if action is not None:
+        return _leapfrog_action(u, P, geo, beta, n_steps, dt, action, native)
     u = u.clone()
     P = P + 0.5 * dt * gauge_force(u, geo, beta)
     for k in range(n_steps):
@@ -70,16 +76,40 @@ def leapfrog(u: torch.Tensor, P: torch.Tensor, geo: LatticeGeometry,
     return u, P
 
 
+def _leapfrog_action(u, P, geo, beta, n_steps, dt, action, native):
+    from .ops import path_gauge_force
+    u = u.clone()
+    P = P.contiguous().clone()  # the native update is in place
+    P = path_gauge_force(u, geo, action, beta, mom=P, dt=0.5 * dt,
+                         native=native)
+    for k in range(n_steps):
+        u = _evolve_u(u, P, geo, dt, native=native)
+        w = 0.5 if k == n_steps - 1 else 1.0
+        P = path_gauge_force(u, geo, action, beta, mom=P, dt=w * dt,
+                             native=native)
+    return u, P
+
+
 def hmc_trajectory(u: torch.Tensor, geo: LatticeGeometry, beta: float,
                    n_md: int = 10, tau: float = 1.0,
-                   seed: Optional[int] = None) -> Tuple[torch.Tensor, bool, float]:
+                   seed: Optional[int] = None, action=None,
+                   native=None) -> Tuple[torch.Tensor, bool, float]:
     """One HMC trajectory with Metropolis accept. Returns
-    (new_u, accepted, dH)."""
+    (new_u, accepted, dH). With a LoopAction `action` the Hamiltonian and
+    the force are those of that action (loop_action / path_gauge_force)."""
     dt = tau / n_md
     P = random_momentum(geo, u.device, seed, u.dtype)
-    H0 = mom_action(P) + gauge_action(u, geo, beta)
-    u1, P1 = leapfrog(u, P, geo, beta, n_md, dt)
-    H1 = mom_action(P1) + gauge_action(u1, geo, beta)
+    if action is None:
+        H0 = mom_action(P) + gauge_action(u, geo, beta)
+        u1, P1 = leapfrog(u, P, geo, beta, n_md, dt)
+        H1 = mom_action(P1) + gauge_action(u1, geo, beta)
+    else:
+        from .ops import loop_action
+        H0 = mom_action(P) + loop_action(u, geo, action, beta, native=native)
+        u1, P1 = leapfrog(u, P, geo, beta, n_md, dt, action=action,
+                          native=native)
+        H1 = mom_action(P1) + loop_action(u1, geo, action, beta,
+                                          native=native)
     dH = H1 - H0
     g = torch.Generator()
     if seed is not None:
@@ -89,7 +119,22 @@ def hmc_trajectory(u: torch.Tensor, geo: LatticeGeometry, beta: float,
 
 
 def _evolve_u(u: torch.Tensor, P: torch.Tensor, geo: LatticeGeometry,
-              dt: float) -> torch.Tensor:
+              dt: float, native=None) -> torch.Tensor:
+    """U <- exp(dt P) U; through the HIP k_expmul kernel where the native
+    gauge-force flag is on and the field eligible."""
+    from .ops import _native_flag
+    if _native_flag(native):
+        from .ops import gauge_native_eligible
+        if gauge_native_eligible(u, native) and P.dtype == u.dtype:
+            from ..ops.dispatch import hip_ext
+            ext = hip_ext()
+            uc = u.contiguous()
+            Zc = (dt * P).contiguous()
+            out = torch.empty_like(uc)
+            for mu in range(4):
+                ext.flow_expmul_dir(out, uc, Zc, list(geo.dims),
+                                    geo.parity_offset, geo.volume_cb, mu)
+            return out
     U = _to_lex(u, geo)
     Pl = _to_lex(P, geo)
     return _from_lex(exp_su3(Pl, dt) @ U, geo)

@@ -98,12 +98,20 @@ def project_ta(M: torch.Tensor) -> torch.Tensor:
     return A - tr[..., None, None] * eye
 
 
-def gauge_force(u: torch.Tensor, geo: LatticeGeometry, beta: float) -> torch.Tensor:
+def gauge_force(u: torch.Tensor, geo: LatticeGeometry, beta: float,
+                native=None) -> torch.Tensor:
     """Wilson-action MD force (ref: lib/gauge_force.cu), normalized for
     OUR Hamiltonian convention H = -sum tr P^2 + S(U), Udot = P U:
     energy conservation then requires Pdot = F = -(beta/6) TA[U staple^d]
     (TA = project_ta; derivation: tr(P TA[M]) = Re tr(P M), and
-    dS/dt = -(beta/3) sum Re tr(P U staple^d))."""
+    dS/dt = -(beta/3) sum Re tr(P U staple^d)). With the native gauge-force
+    flag on (native / QUDA_AMD_NATIVE_GAUGE_FORCE) and an eligible field
+    the path-table HIP kernel computes it."""
+    if _native_flag(native):
+        from .paths import LoopAction, force_table
+        table = force_table(LoopAction.wilson())
+        if gauge_path_eligible(u, table, native):
+            return _path_native(u, geo, table, -(beta / 6.0), ta=True)
     U = _to_lex(u, geo)
     F = torch.empty_like(U)
     for mu in range(4):
@@ -400,13 +408,36 @@ def path_product(u: torch.Tensor, geo: LatticeGeometry,
     return P
 
 
+def loop_traces(u: torch.Tensor, geo: LatticeGeometry, paths,
+                native=None) -> list:
+    """[sum_x tr P_i(x)] per closed path, globally summed, unnormalized
+    (the computeGaugeLoopTraceQuda role). With the native gauge-force flag
+    on and an eligible call the per-site traces come from the HIP
+    k_loop_trace kernel and torch.sum adds them up."""
+    from ..parallel import comms
+    if loop_trace_eligible(u, paths, native):
+        return loop_trace_sites(u, geo, paths).sum(dim=(1, 2)).tolist()
+    out = []
+    for p in paths:
+        P = path_product(u, geo, p)
+        s = torch.diagonal(P, dim1=-2, dim2=-1).sum(-1).sum()
+        out.append(complex(comms.allreduce_sum(s.real.item()),
+                           comms.allreduce_sum(s.imag.item())))
+    return out
+
+
 def loop_trace(u: torch.Tensor, geo: LatticeGeometry, paths,
-               coeffs=None) -> complex:
+               coeffs=None, native=None) -> complex:
     """sum_i c_i <tr P_i>/3 over closed paths, globally averaged (the
-    gaugeLoopTraceQuda role). Default coefficients 1."""
+    gaugeLoopTraceQuda role). Default coefficients 1. `native` routes the
+    traces through the HIP kernel (see loop_traces)."""
     from ..parallel import comms
     coeffs = coeffs or [1.0] * len(paths)
     tot = 0.0 + 0.0j
+    if loop_trace_eligible(u, paths, native):
+        for c, s in zip(coeffs, loop_traces(u, geo, paths, native)):
+            tot += c * s / 3.0 / geo.volume
+        return tot
     n = comms.allreduce_sum(float(geo.volume))
     for c, p in zip(coeffs, paths):
         P = path_product(u, geo, p)
@@ -447,15 +478,22 @@ def improved_gauge_action(u: torch.Tensor, geo: LatticeGeometry,
 
 
 def improved_gauge_force(u: torch.Tensor, geo: LatticeGeometry,
-                         beta: float, *, c1: float = -1.0 / 12.0
-                         ) -> torch.Tensor:
+                         beta: float, *, c1: float = -1.0 / 12.0,
+                         native=None) -> torch.Tensor:
     """Force of the improved action by reverse-mode differentiation of
     the loop traces (single-rank; the plaquette-only force keeps the
     analytic multi-rank path). Same validated convention as
     autograd_fermion_force: F = (1/2) TA[U g^dag] with g the torch
     Wirtinger grad of S — c1=0 reproduces gauge_force exactly and the
-    tests check finite differences + dH conservation."""
+    tests check finite differences + dH conservation. With the native
+    gauge-force flag on and an eligible field the path-table HIP kernel
+    computes the same force analytically instead."""
     from ..parallel import comms
+    if _native_flag(native):
+        from .paths import LoopAction, force_table
+        table = force_table(LoopAction.symanzik(c1))
+        if gauge_path_eligible(u, table, native):
+            return _path_native(u, geo, table, -(beta / 6.0), ta=True)
     assert comms.comm_size() == 1, "autograd gauge force is single-rank"
     u_req = u.detach().clone().requires_grad_(True)
     s = _action_autograd(u_req, geo, beta, c1)
@@ -625,3 +663,146 @@ def topological_charge_density(u: torch.Tensor, geo: LatticeGeometry
     q = (trprod((0, 1), (2, 3)) - trprod((0, 2), (1, 3))
          + trprod((0, 3), (1, 2)))
     return q / (4.0 * math.pi ** 2)
+
+
+# ---------------------------------------------------------------------------
+# path-table force, path product and loop traces (csrc/gauge_path.hip; the
+# computeGaugeForceQuda / computeGaugePathQuda / computeGaugeLoopTraceQuda
+# roles). Opt-in: QUDA_AMD_NATIVE_GAUGE_FORCE=1 or native=True.
+# ---------------------------------------------------------------------------
+
+def native_gauge_force_default() -> bool:
+    """QUDA_AMD_NATIVE_GAUGE_FORCE=1 opts into the HIP path-table kernels
+    (default off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_GAUGE_FORCE", "0") == "1"
+
+
+def _native_flag(native) -> bool:
+    return native_gauge_force_default() if native is None else bool(native)
+
+
+def gauge_native_eligible(u: torch.Tensor, native=None) -> bool:
+    """True when a gauge-shaped complex128 GPU tensor of a single-rank run
+    may take the native HMC kernels: the flag is on (native, or the
+    environment when native is None). Everything else, an explicit
+    native=True included, takes the torch path unchanged."""
+    from ..parallel import comms
+    return bool(_native_flag(native) and u.device.type == "cuda"
+                and u.dtype == torch.complex128 and comms.comm_mask() == 0)
+
+
+def gauge_path_eligible(u: torch.Tensor, action, native=None) -> bool:
+    """gauge_native_eligible and the table within the kernel's limits:
+    tails of at most 7 steps, at most 64 tails per direction."""
+    from .paths import as_table
+    return bool(gauge_native_eligible(u, native)
+                and as_table(action).native_ok)
+
+
+def loop_trace_eligible(u: torch.Tensor, paths, native=None) -> bool:
+    """gauge_native_eligible and every loop closed, of 1 to 8 steps."""
+    from .paths import MAX_LOOP, displacement
+    if not gauge_native_eligible(u, native) or len(paths) == 0:
+        return False
+    for p in paths:
+        if not (1 <= len(p) <= MAX_LOOP) or any(
+                s == 0 or abs(s) > 4 for s in p) or any(displacement(p)):
+            return False
+    return True
+
+
+def _path_native(u: torch.Tensor, geo: LatticeGeometry, table, scale: float,
+                 ta: bool, out: torch.Tensor = None, dt: float = 1.0
+                 ) -> torch.Tensor:
+    """The four k_gauge_path launches. With `out` given the result is
+    accumulated into it in place: out += dt * result."""
+    from ..ops.dispatch import hip_ext
+    ext = hip_ext()
+    steps, lens, coefs = table.on(u.device)
+    uc = u.contiguous()
+    acc = out is not None
+    if acc:
+        assert (out.is_contiguous() and out.shape == u.shape
+                and out.dtype == u.dtype and out.device == u.device), \
+            "fused update needs a contiguous tensor shaped like u"
+    else:
+        out = torch.empty_like(uc)
+    for mu in range(4):
+        ext.gauge_path_dir(out, uc, steps, lens, coefs, list(geo.dims),
+                           geo.parity_offset, geo.volume_cb, mu, float(scale),
+                           float(dt), bool(ta), acc)
+    return out
+
+
+def path_gauge_force(u: torch.Tensor, geo: LatticeGeometry, action,
+                     beta: float, *, mom: torch.Tensor = None,
+                     dt: float = None, native=None) -> torch.Tensor:
+    """MD force of any LoopAction (or ForceTable), F_mu(x) =
+    -(beta/6) TA[U_mu(x) sum_p c_p T_p(x+mu)]: the HIP path-table kernel
+    when eligible, paths.path_force_reference otherwise. With mom and dt
+    the updated momentum mom + dt*F is returned instead (the reference's
+    computeGaugeForceQuda behaviour); the native path updates mom in
+    place in the same pass."""
+    from .paths import as_table, path_force_reference
+    assert (mom is None) == (dt is None), "give mom and dt together"
+    table = as_table(action)
+    if gauge_path_eligible(u, table, native):
+        if mom is None:
+            return _path_native(u, geo, table, -(beta / 6.0), ta=True)
+        return _path_native(u, geo, table, -(beta / 6.0), ta=True, out=mom,
+                            dt=dt)
+    F = path_force_reference(u, geo, table, beta)
+    return F if mom is None else mom + dt * F
+
+
+def path_gauge_product(u: torch.Tensor, geo: LatticeGeometry, action,
+                       scale: float = 1.0, *, out: torch.Tensor = None,
+                       native=None) -> torch.Tensor:
+    """out_mu(x) = scale * U_mu(x) sum_p c_p T_p(x+mu) for the tails of a
+    LoopAction's force table or of an explicit ForceTable (the
+    computeGaugePathQuda role). With `out` given the product is added to
+    it (in place on the native path)."""
+    from .paths import as_table, path_product_reference
+    table = as_table(action)
+    if gauge_path_eligible(u, table, native):
+        return _path_native(u, geo, table, scale, ta=False, out=out)
+    res = path_product_reference(u, geo, table, scale)
+    return res if out is None else out + res
+
+
+def loop_trace_sites(u: torch.Tensor, geo: LatticeGeometry, paths
+                     ) -> torch.Tensor:
+    """[n_loops, 2, Vcb] complex128 per-site traces tr P_i(x) from the HIP
+    k_loop_trace kernel; callers check loop_trace_eligible first."""
+    from ..ops.dispatch import hip_ext
+    from .paths import pack_paths
+    steps, lens = pack_paths(paths)
+    steps, lens = steps.to(u.device), lens.to(u.device)
+    tr = torch.empty((len(paths), 2, geo.volume_cb), dtype=u.dtype,
+                     device=u.device)
+    hip_ext().gauge_loop_trace(tr, u.contiguous(), steps, lens,
+                               list(geo.dims), geo.parity_offset,
+                               geo.volume_cb)
+    return tr
+
+
+def loop_action(u: torch.Tensor, geo: LatticeGeometry, action, beta: float,
+                native=None) -> float:
+    """S = beta sum_i c_i sum_x (1 - Re tr P_i(x)/3) of any LoopAction from
+    its loop traces (global). Equals improved_gauge_action for
+    symanzik(c1) and gauge_action for wilson()."""
+    from ..parallel import comms
+    if loop_trace_eligible(u, action.loops, native):
+        sums = loop_trace_sites(u, geo, action.loops).real.sum(dim=(1, 2))
+        s = 0.0
+        for c, t in zip(action.coeffs, sums.tolist()):
+            s += c * (geo.volume - t / 3.0)
+        return beta * s
+    n = comms.allreduce_sum(float(geo.volume))
+    s = 0.0
+    for c, p in zip(action.coeffs, action.loops):
+        P = path_product(u, geo, p)
+        tr = torch.diagonal(P, dim1=-2, dim2=-1).sum(-1).real.sum().item()
+        s += c * (n - comms.allreduce_sum(tr) / 3.0)
+    return beta * s

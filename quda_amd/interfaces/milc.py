@@ -60,8 +60,11 @@ def qudaLoadKSLink(coeffs=None):
     return api.compute_ks_link_quda(coeffs)
 
 
-def qudaGaugeForce(beta: float):
-    return api.compute_gauge_force_quda(beta)
+def qudaGaugeForce(beta: float, action=None, mom=None, dt=None, native=None):
+    """Wilson force by default; `action` (a gauge.paths.LoopAction) selects
+    an improved action, mom and dt the fused momentum update."""
+    return api.compute_gauge_force_quda(beta, action=action, mom=mom, dt=dt,
+                                        native=native)
 
 
 def qudaUpdateU(mom: torch.Tensor, dt: float) -> None:
@@ -268,10 +271,14 @@ def qudaPolyakovLoop(direction: int = 3) -> complex:
     return polyakov_loop(api._R.u_complex, api._R.geo)
 
 
-def qudaGaugeLoopTrace(paths, coeffs=None):
-    """Batched Wilson-loop traces (ref qudaGaugeLoopTracePhased)."""
-    from ..gauge import loop_trace
-    return loop_trace(api._R.u_complex, api._R.geo, paths, coeffs)
+def qudaGaugeLoopTrace(paths, coeffs=None, native=None):
+    """Batched Wilson-loop traces (ref qudaGaugeLoopTracePhased):
+    sum_i c_i <tr P_i>/3, through api.compute_gauge_loop_trace_quda."""
+    geo = api._R.geo
+    from ..parallel import comms
+    n = comms.allreduce_sum(float(geo.volume))
+    return sum(api.compute_gauge_loop_trace_quda(
+        paths, coeffs, 1.0 / (3.0 * n), native=native), 0.0 + 0.0j)
 
 
 # ---------------------------------------------------------------------------
@@ -402,10 +409,12 @@ def qudaGaugeLoopTracePhased(paths, coeffs=None):
         _with_phases(False)
 
 
-def qudaGaugeForcePhased(beta: float):
+def qudaGaugeForcePhased(beta: float, action=None, mom=None, dt=None,
+                         native=None):
     _with_phases(True)
     try:
-        return qudaGaugeForce(beta)
+        return qudaGaugeForce(beta, action=action, mom=mom, dt=dt,
+                              native=native)
     finally:
         _with_phases(False)
 
