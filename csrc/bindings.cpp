@@ -433,10 +433,13 @@ static void twist_apply(at::Tensor out, at::Tensor out_n, at::Tensor in,
   check_launch("twist_apply");
 }
 
-static void dwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
-                 at::Tensor in_n, at::Tensor x, at::Tensor x_n,
-                 int64_t Vcb4, int64_t Ls, bool xpay, bool dagger, double a,
-                 double alpha, double beta, double mf, int64_t kind) {
+// 5th-dimension family (csrc/dslash_dwf.h): the call base of dwf5 / zdwf5 /
+// eofa5 from the tensors
+static Dwf5Call dwf5_base(const at::Tensor &out, const at::Tensor &out_n,
+                          const at::Tensor &in, const at::Tensor &in_n,
+                          const at::Tensor &x, const at::Tensor &x_n,
+                          int64_t Vcb4, int64_t Ls, bool xpay, bool dagger,
+                          double a, int64_t kind) {
   Dwf5Call c{};
   long stride = Vcb4 * Ls;
   c.out = field_of(out, out_n, stride);
@@ -447,13 +450,66 @@ static void dwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
   c.xpay = xpay;
   c.dagger = dagger;
   c.a = a;
+  c.prec = prec_of(out);
+  c.kind = (int)kind;
+  return c;
+}
+
+static void dwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                 at::Tensor in_n, at::Tensor x, at::Tensor x_n,
+                 int64_t Vcb4, int64_t Ls, bool xpay, bool dagger, double a,
+                 double alpha, double beta, double mf, int64_t kind) {
+  Mobius5Call c{dwf5_base(out, out_n, in, in_n, x, x_n, Vcb4, Ls, xpay,
+                          dagger, a, kind),
+                alpha, beta, mf};
+  TORCH_CHECK(launch_dwf5(c, stream()), "dwf5: no kernel for this precision");
+  check_launch("dwf5");
+}
+
+// table: the ZCoef bytes (ops/dispatch.py _zpack), a host uint8 tensor
+static void zdwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                  at::Tensor in_n, at::Tensor x, at::Tensor x_n,
+                  int64_t Vcb4, int64_t Ls, bool xpay, double a_re,
+                  double a_im, int64_t kind, at::Tensor table) {
+  TORCH_CHECK(Ls >= 1 && Ls <= QA_ZMAX, "zdwf5: Ls = ", Ls, " outside 1..",
+              QA_ZMAX);
+  TORCH_CHECK(table.device().is_cpu() && table.scalar_type() == at::kByte &&
+                  table.is_contiguous() &&
+                  table.numel() == (int64_t)sizeof(ZCoef),
+              "zdwf5: table is not the ", sizeof(ZCoef),
+              " bytes of a host ZCoef");
+  ZDwf5Call c{dwf5_base(out, out_n, in, in_n, x, x_n, Vcb4, Ls, xpay, false,
+                        a_re, kind),
+              a_im, (const ZCoef *)table.data_ptr()};
+  TORCH_CHECK(launch_zdwf5(c, stream()),
+              "zdwf5: double or single only, or the table could not be "
+              "staged");
+  check_launch("zdwf5");
+}
+
+static void eofa5(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                  at::Tensor in_n, at::Tensor x, at::Tensor x_n,
+                  int64_t Vcb4, int64_t Ls, bool xpay, bool dagger, double a,
+                  double alpha, double beta, double mf,
+                  std::vector<double> u, std::vector<double> w, double sh,
+                  int64_t pm, int64_t kind) {
+  TORCH_CHECK(Ls >= 1 && Ls <= QA_ZMAX, "eofa5: Ls = ", Ls, " outside 1..",
+              QA_ZMAX);
+  Eofa5Call c{};
+  c.f = dwf5_base(out, out_n, in, in_n, x, x_n, Vcb4, Ls, xpay, dagger, a,
+                  kind);
   c.alpha = alpha;
   c.beta = beta;
   c.mf = mf;
-  c.prec = prec_of(out);
-  c.kind = (int)kind;
-  launch_dwf5(c, stream());
-  check_launch("dwf5");
+  for (int s = 0; s < (int)Ls; ++s) {
+    if (s < (int)u.size()) c.u[s] = u[s];
+    if (s < (int)w.size()) c.w[s] = w[s];
+  }
+  c.sh = sh;
+  c.pm = (int)pm;
+  TORCH_CHECK(launch_eofa5(c, stream()),
+              "eofa5: double, single or half only");
+  check_launch("eofa5");
 }
 
 // Fused domain-wall kernel (csrc/dslash_dwf_fused.h). Every argument is
@@ -541,85 +597,6 @@ static void dwf_fused(at::Tensor out, at::Tensor out_n, at::Tensor in,
   TORCH_CHECK(launch_dwf_fused(c, stream()),
               "dwf_fused: no kernel for this configuration");
   check_launch("dwf_fused");
-}
-
-static void zdwf5(at::Tensor out, at::Tensor out_n, at::Tensor in,
-                  at::Tensor in_n, at::Tensor x, at::Tensor x_n,
-                  int64_t Vcb4, int64_t Ls, bool xpay, double a_re,
-                  double a_im, int64_t kind,
-                  std::vector<double> au, std::vector<double> al,
-                  std::vector<double> wu, std::vector<double> wl,
-                  std::vector<int64_t> su, std::vector<int64_t> sl,
-                  std::vector<int64_t> ord_u, std::vector<int64_t> ord_l,
-                  std::vector<double> diu, std::vector<double> eu,
-                  std::vector<double> dil, std::vector<double> el,
-                  double cwu_re, double cwu_im, double cwl_re, double cwl_im) {
-  TORCH_CHECK(Ls <= QA_ZMAX, "zMobius Ls > ", QA_ZMAX);
-  ZCoef zc{};
-  auto put2 = [&](double dst[][2], const std::vector<double> &v) {
-    for (int s = 0; s < (int)Ls && 2 * s + 1 < (int)v.size(); ++s) {
-      dst[s][0] = v[2 * s];
-      dst[s][1] = v[2 * s + 1];
-    }
-  };
-  put2(zc.au, au); put2(zc.al, al); put2(zc.wu, wu); put2(zc.wl, wl);
-  put2(zc.diu, diu); put2(zc.eu, eu); put2(zc.dil, dil); put2(zc.el, el);
-  for (int s = 0; s < (int)Ls; ++s) {
-    if (s < (int)su.size()) zc.su[s] = (int)su[s];
-    if (s < (int)sl.size()) zc.sl[s] = (int)sl[s];
-    if (s < (int)ord_u.size()) zc.ord_u[s] = (int)ord_u[s];
-    if (s < (int)ord_l.size()) zc.ord_l[s] = (int)ord_l[s];
-  }
-  zc.cwu[0] = cwu_re; zc.cwu[1] = cwu_im;
-  zc.cwl[0] = cwl_re; zc.cwl[1] = cwl_im;
-  ZDwf5Call c{};
-  long stride = Vcb4 * Ls;
-  c.out = field_of(out, out_n, stride);
-  c.in = field_of(in, in_n, stride);
-  c.x = field_of(x, x_n, stride);
-  c.Vcb4 = Vcb4;
-  c.Ls = (int)Ls;
-  c.xpay = xpay;
-  c.a_re = a_re;
-  c.a_im = a_im;
-  c.prec = prec_of(out);
-  c.kind = (int)kind;
-  TORCH_CHECK(c.prec != 2, "zdwf5: half precision unsupported");
-  c.zc = &zc;
-  launch_zdwf5(c, stream());
-  check_launch("zdwf5");
-}
-
-static void eofa5(at::Tensor out, at::Tensor out_n, at::Tensor in,
-                  at::Tensor in_n, at::Tensor x, at::Tensor x_n,
-                  int64_t Vcb4, int64_t Ls, bool xpay, bool dagger, double a,
-                  double alpha, double beta, double mf,
-                  std::vector<double> u, std::vector<double> w, double sh,
-                  int64_t pm, int64_t kind) {
-  TORCH_CHECK(Ls <= 32, "eofa5: Ls > 32");
-  Eofa5Call c{};
-  long stride = Vcb4 * Ls;
-  c.out = field_of(out, out_n, stride);
-  c.in = field_of(in, in_n, stride);
-  c.x = field_of(x, x_n, stride);
-  c.Vcb4 = Vcb4;
-  c.Ls = (int)Ls;
-  c.xpay = xpay;
-  c.dagger = dagger;
-  c.a = a;
-  c.alpha = alpha;
-  c.beta = beta;
-  c.mf = mf;
-  for (int s = 0; s < (int)Ls; ++s) {
-    if (s < (int)u.size()) c.u[s] = u[s];
-    if (s < (int)w.size()) c.w[s] = w[s];
-  }
-  c.sh = sh;
-  c.pm = (int)pm;
-  c.prec = prec_of(out);
-  c.kind = (int)kind;
-  launch_eofa5(c, stream());
-  check_launch("eofa5");
 }
 
 static void set_dslash_block(int64_t b) {

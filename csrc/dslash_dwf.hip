@@ -1,110 +1,124 @@
 // DWF/Moebius 5th-dimension TU (all precisions)
+#include <type_traits>
+
 #include "dslash_dwf.h"
 #include "launch_setup.h"
+#include "table_cache.h"
 
+namespace {
+
+// Kernel pairs of the three families. HOP_5D: the hop runs a thread per 5-d
+// site (the EOFA hop needs all of s for its rank-1 dot and runs per 4-d
+// site, like every inverse).
 template <typename Prec>
-static void dwf5_t(const Dwf5Call &c, hipStream_t st) {
-  using R = typename Prec::Real;
+struct MobiusK {
+  static constexpr bool HOP_5D = true;
+  template <bool XPAY, bool DAG>
+  static auto hop() { return &k_dslash5<Prec, XPAY, DAG>; }
+  template <bool XPAY, bool DAG>
+  static auto inv() { return &k_m5inv<Prec, XPAY, DAG>; }
+};
+template <typename Prec>
+struct ZMobiusK {  // the dagger lives in the tables
+  static constexpr bool HOP_5D = true;
+  template <bool XPAY, bool>
+  static auto hop() { return &k_zdslash5<Prec, XPAY>; }
+  template <bool XPAY, bool>
+  static auto inv() { return &k_zm5inv<Prec, XPAY>; }
+};
+template <typename Prec>
+struct EofaK {
+  static constexpr bool HOP_5D = false;
+  template <bool XPAY, bool DAG>
+  static auto hop() { return &k_m5_eofa<Prec, XPAY, DAG>; }
+  template <bool XPAY, bool DAG>
+  static auto inv() { return &k_m5inv_eofa<Prec, XPAY, DAG>; }
+};
+
+// The one launch of the family: picks the grid and the XPAY/DAG
+// instantiation; `tail` are the kernel arguments after (out, in, x, Vcb4, Ls).
+template <typename Prec, template <typename> class K, typename... Tail>
+bool launch5(const Dwf5Call &c, hipStream_t st, Tail... tail) {
   auto out = spinor_acc<Prec>(c.out);
   auto in = spinor_acc<Prec>(c.in);
   auto x = spinor_acc<Prec>(c.x);
-  int blk = 256;
-  R a = (R)c.a, al = (R)c.alpha, be = (R)c.beta, mf = (R)c.mf;
-
-#define QA_D5(XPAY, DAG)                                                      \
-  if (c.kind == 0) {                                                          \
-    long n = c.Vcb4 * c.Ls;                                                   \
-    hipLaunchKernelGGL((k_dslash5<Prec, XPAY, DAG>),                          \
-                       dim3((int)((n + blk - 1) / blk)), dim3(blk), 0, st,    \
-                       out, in, x, c.Vcb4, c.Ls, a, al, be, mf);              \
-  } else {                                                                    \
-    hipLaunchKernelGGL((k_m5inv<Prec, XPAY, DAG>),                            \
-                       dim3((int)((c.Vcb4 + blk - 1) / blk)), dim3(blk), 0,   \
-                       st, out, in, x, c.Vcb4, c.Ls, a, al, be, mf);          \
-  }
-
-  if (c.xpay) { if (c.dagger) QA_D5(true, true) else QA_D5(true, false) }
-  else        { if (c.dagger) QA_D5(false, true) else QA_D5(false, false) }
-#undef QA_D5
-}
-
-void launch_dwf5(const Dwf5Call &c, hipStream_t st) {
-  switch (c.prec) {
-    case 0: dwf5_t<PrecDouble>(c, st); break;
-    case 1: dwf5_t<PrecSingle>(c, st); break;
-    case 2: dwf5_t<PrecHalf>(c, st); break;
-    case 3: dwf5_t<PrecQuarter>(c, st); break;
-  }
+  const int blk = 256;
+  auto go = [&](auto xpay, auto dag) {
+    constexpr bool X = decltype(xpay)::value, D = decltype(dag)::value;
+    if (c.kind == 0) {
+      long n = K<Prec>::HOP_5D ? c.Vcb4 * c.Ls : c.Vcb4;
+      hipLaunchKernelGGL((K<Prec>::template hop<X, D>()),
+                         dim3((int)((n + blk - 1) / blk)), dim3(blk), 0, st,
+                         out, in, x, c.Vcb4, c.Ls, tail...);
+    } else {
+      hipLaunchKernelGGL((K<Prec>::template inv<X, D>()),
+                         dim3((int)((c.Vcb4 + blk - 1) / blk)), dim3(blk), 0,
+                         st, out, in, x, c.Vcb4, c.Ls, tail...);
+    }
+  };
+  std::true_type T;
+  std::false_type F;
+  if (c.xpay) { if (c.dagger) go(T, T); else go(T, F); }
+  else        { if (c.dagger) go(F, T); else go(F, F); }
+  return true;
 }
 
 template <typename Prec>
-static void zdwf5_t(const ZDwf5Call &c, const ZCoef *dzc, hipStream_t st) {
+bool dwf5_t(const Mobius5Call &c, hipStream_t st) {
   using R = typename Prec::Real;
-  auto out = spinor_acc<Prec>(c.out);
-  auto in = spinor_acc<Prec>(c.in);
-  auto x = spinor_acc<Prec>(c.x);
-  int blk = 256;
-  R ar = (R)c.a_re, ai = (R)c.a_im;
-#define QA_Z5(XPAY)                                                           \
-  if (c.kind == 0) {                                                          \
-    long n = c.Vcb4 * c.Ls;                                                   \
-    hipLaunchKernelGGL((k_zdslash5<Prec, XPAY>),                              \
-                       dim3((int)((n + blk - 1) / blk)), dim3(blk), 0, st,    \
-                       out, in, x, c.Vcb4, c.Ls, ar, ai, dzc);                \
-  } else {                                                                    \
-    hipLaunchKernelGGL((k_zm5inv<Prec, XPAY>),                                \
-                       dim3((int)((c.Vcb4 + blk - 1) / blk)), dim3(blk), 0,   \
-                       st, out, in, x, c.Vcb4, c.Ls, ar, ai, dzc);            \
-  }
-  if (c.xpay) QA_Z5(true) else QA_Z5(false)
-#undef QA_Z5
-}
-
-void launch_zdwf5(const ZDwf5Call &c, hipStream_t st) {
-  // stage the host-assembled table into a persistent device buffer
-  // (stream-ordered: the async copy precedes the kernel on the same stream)
-  static ZCoef *dzc = nullptr;
-  if (!dzc) (void)hipMalloc(&dzc, sizeof(ZCoef));
-  (void)hipMemcpyAsync(dzc, c.zc, sizeof(ZCoef), hipMemcpyHostToDevice, st);
-  switch (c.prec) {
-    case 0: zdwf5_t<PrecDouble>(c, dzc, st); break;
-    case 1: zdwf5_t<PrecSingle>(c, dzc, st); break;
-  }
+  return launch5<Prec, MobiusK>(c.f, st, (R)c.f.a, (R)c.alpha, (R)c.beta,
+                                (R)c.mf);
 }
 
 template <typename Prec>
-static void eofa5_t(const Eofa5Call &c, hipStream_t st) {
+bool zdwf5_t(const ZDwf5Call &c, hipStream_t st) {
   using R = typename Prec::Real;
-  auto out = spinor_acc<Prec>(c.out);
-  auto in = spinor_acc<Prec>(c.in);
-  auto x = spinor_acc<Prec>(c.x);
+  auto *dzc = (const ZCoef *)device_table(c.zc, sizeof(ZCoef));
+  if (!dzc) return false;
+  return launch5<Prec, ZMobiusK>(c.f, st, (R)c.f.a, (R)c.a_im, dzc);
+}
+
+template <typename Prec>
+bool eofa5_t(const Eofa5Call &c, hipStream_t st) {
+  using R = typename Prec::Real;
   EofaVec ev{};
-  for (int s_ = 0; s_ < c.Ls && s_ < QA_ZMAX; ++s_) {
-    ev.u[s_] = c.u[s_];
-    ev.w[s_] = c.w[s_];
+  for (int s = 0; s < c.f.Ls && s < QA_ZMAX; ++s) {
+    ev.u[s] = c.u[s];
+    ev.w[s] = c.w[s];
   }
   ev.sh = c.sh;
   ev.pm = c.pm;
-  int blk = 256;
-  int grid = (int)((c.Vcb4 + blk - 1) / blk);
-  R a = (R)c.a, al = (R)c.alpha, be = (R)c.beta, mf = (R)c.mf;
-#define QA_E5(XPAY, DAG)                                                      \
-  if (c.kind == 0)                                                            \
-    hipLaunchKernelGGL((k_m5_eofa<Prec, XPAY, DAG>), dim3(grid), dim3(blk),   \
-                       0, st, out, in, x, c.Vcb4, c.Ls, a, al, be, mf, ev);   \
-  else                                                                        \
-    hipLaunchKernelGGL((k_m5inv_eofa<Prec, XPAY, DAG>), dim3(grid),           \
-                       dim3(blk), 0, st, out, in, x, c.Vcb4, c.Ls, a, al,     \
-                       be, mf, ev);
-  if (c.xpay) { if (c.dagger) QA_E5(true, true) else QA_E5(true, false) }
-  else        { if (c.dagger) QA_E5(false, true) else QA_E5(false, false) }
-#undef QA_E5
+  return launch5<Prec, EofaK>(c.f, st, (R)c.f.a, (R)c.alpha, (R)c.beta,
+                              (R)c.mf, ev);
 }
 
-void launch_eofa5(const Eofa5Call &c, hipStream_t st) {
-  switch (c.prec) {
-    case 0: eofa5_t<PrecDouble>(c, st); break;
-    case 1: eofa5_t<PrecSingle>(c, st); break;
-    case 2: eofa5_t<PrecHalf>(c, st); break;
+}  // namespace
+
+bool launch_dwf5(const Mobius5Call &c, hipStream_t st) {
+  switch (c.f.prec) {
+    case 0: return dwf5_t<PrecDouble>(c, st);
+    case 1: return dwf5_t<PrecSingle>(c, st);
+    case 2: return dwf5_t<PrecHalf>(c, st);
+    case 3: return dwf5_t<PrecQuarter>(c, st);
   }
+  return false;
+}
+
+// double/single only: k_zm5inv's per-half read-modify-write would re-round
+// the other chirality half of a block-float site
+bool launch_zdwf5(const ZDwf5Call &c, hipStream_t st) {
+  switch (c.f.prec) {
+    case 0: return zdwf5_t<PrecDouble>(c, st);
+    case 1: return zdwf5_t<PrecSingle>(c, st);
+  }
+  return false;
+}
+
+bool launch_eofa5(const Eofa5Call &c, hipStream_t st) {
+  switch (c.f.prec) {
+    case 0: return eofa5_t<PrecDouble>(c, st);
+    case 1: return eofa5_t<PrecSingle>(c, st);
+    case 2: return eofa5_t<PrecHalf>(c, st);
+  }
+  return false;
 }

@@ -1,44 +1,19 @@
 // Fused domain-wall TU: 4-d hop + dense per-chirality s-stage in one launch
 // (double/single/half; recon 18 everywhere, recon 12 for single and half)
-#include <cstring>
-#include <map>
-#include <string>
 #include <vector>
 
 #include "dslash_dwf_fused.h"
 #include "launch_setup.h"
+#include "table_cache.h"
 
 namespace {
 
-// Device copy of the two Ls x Ls blocks, converted to the compute type on
-// the host. Operators reuse a handful of matrices for their whole life, so
-// the copies are cached by content: a steady-state launch does no
-// host-to-device transfer.
+// Cached device copy (table_cache.h) of the two Ls x Ls blocks, converted
+// to the compute type on the host.
 template <typename R>
 const R *dwf_fused_w(const double *W, int Ls) {
-  static std::map<std::string, R *> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const size_t n = (size_t)2 * Ls * Ls;
-  std::string key((const char *)&dev, sizeof(dev));
-  key.append((const char *)W, n * sizeof(double));
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  if (cache.size() >= 256) {  // hipFree waits for in-flight kernels
-    for (auto &kv : cache) (void)hipFree(kv.second);
-    cache.clear();
-  }
-  std::vector<R> host(n);
-  for (size_t k = 0; k < n; ++k) host[k] = (R)W[k];
-  R *dptr = nullptr;
-  if (hipMalloc(&dptr, n * sizeof(R)) != hipSuccess) return nullptr;
-  if (hipMemcpy(dptr, host.data(), n * sizeof(R), hipMemcpyHostToDevice) !=
-      hipSuccess) {
-    (void)hipFree(dptr);
-    return nullptr;
-  }
-  cache.emplace(std::move(key), dptr);
-  return dptr;
+  std::vector<R> host(W, W + (size_t)2 * Ls * Ls);
+  return (const R *)device_table(host.data(), host.size() * sizeof(R));
 }
 
 template <typename Prec, int RECON, int NS>

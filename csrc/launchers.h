@@ -232,17 +232,57 @@ void launch_dslash_staggered(const StagDslashCall &c, hipStream_t st);
 void launch_pack_face_stag(const PackCall &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// 5th-dimension family (csrc/dslash_dwf.h): Moebius, zMobius and EOFA share
+// one call base. Each launcher returns false, and launches nothing, when
+// the precision has no instantiation or a table could not be staged.
+#define QA_ZMAX 32  // largest Ls of the zMobius and EOFA tables
+
 struct Dwf5Call {
   BlasField out, in, x;  // 5-d single-parity fields (Vcb = chunk stride Ls*Vcb4)
   long Vcb4;
   int Ls;
   bool xpay;
-  bool dagger;
-  double a, alpha, beta, mf;
+  bool dagger;  // zMobius: folded into the tables, stays false
+  double a;     // zMobius: real part
   int prec;
-  int kind;  // 0 = dslash5 (Ds apply), 1 = m5inv
+  int kind;  // 0 = hop (alpha + beta Ds), 1 = its inverse
 };
-void launch_dwf5(const Dwf5Call &c, hipStream_t st);
+
+struct Mobius5Call {  // k_dslash5 / k_m5inv, all four precisions
+  Dwf5Call f;
+  double alpha, beta, mf;
+};
+bool launch_dwf5(const Mobius5Call &c, hipStream_t st);
+
+struct ZCoef {  // host-filled complex coefficient tables (double re/im)
+  // zdslash5: out(s)_upper = au[s]*in(s) + wu[s]*in(su[s]); lower likewise
+  double au[QA_ZMAX][2], al[QA_ZMAX][2];
+  double wu[QA_ZMAX][2], wl[QA_ZMAX][2];
+  int su[QA_ZMAX], sl[QA_ZMAX];
+  // zm5inv: per chirality a sequence order ord[i] = physical slice of step
+  // i and the recursion y[i] = di[i] * (r[i] - e[i] y[i-1]) with di = 1/d;
+  // Sherman-Morrison corner weight cw couples step 0 to the LAST step.
+  int ord_u[QA_ZMAX], ord_l[QA_ZMAX];
+  double diu[QA_ZMAX][2], eu[QA_ZMAX][2], cwu[2];
+  double dil[QA_ZMAX][2], el[QA_ZMAX][2], cwl[2];
+};
+
+struct ZDwf5Call {  // k_zdslash5 / k_zm5inv, double and single
+  Dwf5Call f;
+  double a_im;
+  const ZCoef *zc;  // host table; the launcher runs on its cached device
+                    // copy (csrc/table_cache.h)
+};
+bool launch_zdwf5(const ZDwf5Call &c, hipStream_t st);
+
+struct Eofa5Call {  // k_m5_eofa / k_m5inv_eofa, double, single and half
+  Dwf5Call f;
+  double alpha, beta, mf;
+  double u[QA_ZMAX], w[QA_ZMAX];  // see EofaVec (dslash_dwf.h)
+  double sh;
+  int pm;
+};
+bool launch_eofa5(const Eofa5Call &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // fused domain-wall kernel (csrc/dslash_dwf_fused.h): for all Ls slices,
@@ -343,49 +383,6 @@ struct LoopTraceCall {
   LatDesc lat;
 };
 void launch_loop_trace(const LoopTraceCall &c, hipStream_t st);
-
-#define QA_ZMAX 32
-
-struct ZCoef {  // host-filled complex coefficient tables (double re/im)
-  // zdslash5: out(s)_upper = au[s]*in(s) + wu[s]*in(su[s]); lower likewise
-  double au[QA_ZMAX][2], al[QA_ZMAX][2];
-  double wu[QA_ZMAX][2], wl[QA_ZMAX][2];
-  int su[QA_ZMAX], sl[QA_ZMAX];
-  // zm5inv: per chirality a sequence order ord[i] = physical slice of step
-  // i and the recursion y[i] = di[i] * (r[i] - e[i] y[i-1]) with di = 1/d;
-  // Sherman-Morrison corner weight cw couples step 0 to the LAST step.
-  int ord_u[QA_ZMAX], ord_l[QA_ZMAX];
-  double diu[QA_ZMAX][2], eu[QA_ZMAX][2], cwu[2];
-  double dil[QA_ZMAX][2], el[QA_ZMAX][2], cwl[2];
-};
-
-struct ZDwf5Call {
-  BlasField out, in, x;
-  long Vcb4;
-  int Ls;
-  bool xpay;
-  double a_re, a_im;
-  int prec;
-  int kind;  // 0 = zdslash5, 1 = zm5inv (double/single only)
-  const ZCoef *zc;  // HOST pointer; launcher stages to device
-};
-void launch_zdwf5(const ZDwf5Call &c, hipStream_t st);
-
-struct EofaVec;  // defined in dslash_dwf.h
-struct Eofa5Call {
-  BlasField out, in, x;
-  long Vcb4;
-  int Ls;
-  bool xpay;
-  bool dagger;
-  double a, alpha, beta, mf;
-  double u[32], w[32];  // see EofaVec semantics (m5inv: u = B^-1 u, sh/denom)
-  double sh;
-  int pm;
-  int prec;
-  int kind;  // 0 = m5_eofa, 1 = m5inv_eofa
-};
-void launch_eofa5(const Eofa5Call &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // multigrid transfer, fine Wilson level (csrc/transfer.hip). Double/single.

@@ -695,6 +695,16 @@ def dslash_staggered(out: SpinorField, inp: SpinorField, gauge: GaugeField,
     return out
 
 
+def _gpu_args5(out: SpinorField, inp: SpinorField,
+               x: Optional[SpinorField]):
+    """Leading arguments of the 5th-dimension bindings (dwf5 / zdwf5 /
+    eofa5): fields with their norms, 4-d cb volume, Ls, xpay."""
+    xf = x if x is not None else out
+    return (out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
+            xf.data, norm_or_empty(xf), inp.geo.volume_cb, inp.ls,
+            x is not None)
+
+
 def dwf5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
             mf: float, kind: int, dagger: bool = False, a: float = 1.0,
             x: Optional[SpinorField] = None):
@@ -702,14 +712,9 @@ def dwf5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
     kind=0: out = [a*x +] alpha*in + beta*(Ds in)
     kind=1: out = [x +] a * (alpha + beta*Ds)^{-1} in"""
     Ls = inp.ls
-    xpay = x is not None
     if on_gpu(out, inp):
-        ext = hip_ext()
-        xf = x if x is not None else out
-        ext.dwf5(out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
-                 xf.data, norm_or_empty(xf), inp.geo.volume_cb, Ls,
-                 xpay, bool(dagger), float(a), float(alpha), float(beta),
-                 float(mf), kind)
+        hip_ext().dwf5(*_gpu_args5(out, inp, x), bool(dagger), float(a),
+                       float(alpha), float(beta), float(mf), kind)
         return out
     op5 = ref.dslash5 if kind == 0 else ref.m5inv
     return _finish5(out, op5(inp.to_complex()[0], Ls, alpha, beta, mf, dagger),
@@ -777,6 +782,31 @@ def _ztables(Ls, diag, hop, mf, dagger):
                 cwl_re=cwl.real, cwl_im=cwl.imag)
 
 
+ZMAX = 32  # csrc/launchers.h QA_ZMAX
+
+
+def _zpack(t, Ls):
+    """The _ztables dict laid out as the bytes of csrc ZCoef, in one CPU
+    uint8 tensor (entries past Ls stay zero). ext.zdwf5 checks the size
+    against sizeof(ZCoef)."""
+    import numpy as np
+    if not 1 <= Ls <= ZMAX:
+        raise RuntimeError(f"zMobius tables: Ls = {Ls} outside 1..{ZMAX}")
+    c, i = ("<f8", (ZMAX, 2)), ("<i4", (ZMAX,))
+    z = np.zeros(1, dtype=np.dtype([
+        ("au", *c), ("al", *c), ("wu", *c), ("wl", *c), ("su", *i),
+        ("sl", *i), ("ord_u", *i), ("ord_l", *i), ("diu", *c), ("eu", *c),
+        ("cwu", "<f8", (2,)), ("dil", *c), ("el", *c),
+        ("cwl", "<f8", (2,))]))
+    for k in ("au", "al", "wu", "wl", "diu", "eu", "dil", "el"):
+        z[k][0, :Ls] = np.asarray(t[k], dtype=np.float64).reshape(Ls, 2)
+    for k in ("su", "sl", "ord_u", "ord_l"):
+        z[k][0, :Ls] = t[k]
+    z["cwu"][0] = (t["cwu_re"], t["cwu_im"])
+    z["cwl"][0] = (t["cwl_re"], t["cwl_im"])
+    return torch.from_numpy(z.view(np.uint8))
+
+
 _ztable_cache = {}
 
 
@@ -789,25 +819,16 @@ def zdwf5_op(out: SpinorField, inp: SpinorField, diag, hop, mf: float,
     kind=1: out = [x +] a * (diag + hop*Ds)^{-1} in"""
     Ls = inp.ls
     a = complex(a)
-    xpay = x is not None
     if on_gpu(out, inp):
         key = (tuple(complex(d) for d in diag), tuple(complex(h) for h in hop),
                float(mf), bool(dagger), Ls)
         t = _ztable_cache.get(key)
         if t is None:
-            t = _ztables(Ls, diag, hop, float(mf), bool(dagger))
+            t = _zpack(_ztables(Ls, diag, hop, float(mf), bool(dagger)), Ls)
             if len(_ztable_cache) > 64:
                 _ztable_cache.clear()
             _ztable_cache[key] = t
-        ext = hip_ext()
-        xf = x if x is not None else out
-        ext.zdwf5(out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
-                  xf.data, norm_or_empty(xf), inp.geo.volume_cb, Ls,
-                  xpay, a.real, a.imag, kind,
-                  t["au"], t["al"], t["wu"], t["wl"], t["su"], t["sl"],
-                  t["ord_u"], t["ord_l"], t["diu"], t["eu"], t["dil"],
-                  t["el"], t["cwu_re"], t["cwu_im"], t["cwl_re"],
-                  t["cwl_im"])
+        hip_ext().zdwf5(*_gpu_args5(out, inp, x), a.real, a.imag, kind, t)
         return out
     op5 = ref.zdslash5 if kind == 0 else ref.zm5inv
     return _finish5(out, op5(inp.to_complex()[0], Ls, diag, hop, mf, dagger),
@@ -826,10 +847,7 @@ def eofa5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
     the kernel receives B^-1 u and sh/denom (Sherman-Morrison folded)."""
     import numpy as np
     Ls = inp.ls
-    xpay = x is not None
     if on_gpu(out, inp):
-        ext = hip_ext()
-        xf = x if x is not None else out
         uu = [float(v) for v in u]
         ww = [float(v) for v in w]
         if dagger:
@@ -845,10 +863,9 @@ def eofa5_op(out: SpinorField, inp: SpinorField, alpha: float, beta: float,
             sh_k = sh / den
         else:
             sh_k = sh
-        ext.eofa5(out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
-                  xf.data, norm_or_empty(xf), inp.geo.volume_cb, Ls, xpay,
-                  bool(dagger), float(a), float(alpha), float(beta),
-                  float(mf), uu, ww, float(sh_k), int(pm), kind)
+        hip_ext().eofa5(*_gpu_args5(out, inp, x), bool(dagger), float(a),
+                        float(alpha), float(beta), float(mf), uu, ww,
+                        float(sh_k), int(pm), kind)
         return out
     op5 = ref.m5_eofa if kind == 0 else ref.m5inv_eofa
     return _finish5(out, op5(inp.to_complex()[0], Ls, alpha, beta, mf, sh, pm,

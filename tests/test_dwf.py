@@ -570,3 +570,223 @@ def test_madwf_with_zmobius_inner(setup):
     assert st0.converged and st1.converged
     err = (x1.to_complex() - x0.to_complex()).abs().max().item()
     assert err < 1e-6, err
+
+
+# ---------------------------------------------------------------------------
+# 5th-dimension family: packed zMobius table, epilogues, table cache, refusals
+# ---------------------------------------------------------------------------
+
+def _zcoefs_n(n, shift=0.0):
+    """n zMobius (diag, hop) rows; `shift` gives a second, different set."""
+    b5 = [1.5 + shift + 0.02 * s + (0.1 - 0.03 * s) * 1j for s in range(n)]
+    d4 = 4.0 - M5
+    return [1.0 + b * d4 for b in b5], [(b - 1.0) * d4 - 1.0 for b in b5]
+
+
+@pytest.mark.parametrize("ls", [5, 32])
+@pytest.mark.parametrize("dagger", [False, True])
+def test_zpack_reproduces_ztables(ls, dagger):
+    """The packed table (what ext.zdwf5 copies to the device as a ZCoef)
+    holds every field of the _ztables dict exactly; entries past Ls are 0.
+    The dtype below mirrors csrc/launchers.h ZCoef (QA_ZMAX = 32)."""
+    import numpy as np
+    from quda_amd.ops.dispatch import _zpack, _ztables
+    c, i = ("<f8", (32, 2)), ("<i4", (32,))
+    zcoef = np.dtype([("au", *c), ("al", *c), ("wu", *c), ("wl", *c),
+                      ("su", *i), ("sl", *i), ("ord_u", *i), ("ord_l", *i),
+                      ("diu", *c), ("eu", *c), ("cwu", "<f8", (2,)),
+                      ("dil", *c), ("el", *c), ("cwl", "<f8", (2,))])
+    assert zcoef.itemsize == 4640
+    diag, hop = _zcoefs_n(ls)
+    t = _ztables(ls, diag, hop, MF, dagger)
+    packed = _zpack(t, ls)
+    assert packed.dtype == torch.uint8 and packed.device.type == "cpu"
+    assert packed.is_contiguous() and packed.numel() == zcoef.itemsize
+    z = np.frombuffer(packed.numpy().tobytes(), dtype=zcoef)[0]
+    for k in ("au", "al", "wu", "wl", "diu", "eu", "dil", "el"):
+        assert z[k][:ls].reshape(-1).tolist() == list(t[k]), k
+        assert not z[k][ls:].any(), k
+    for k in ("su", "sl", "ord_u", "ord_l"):
+        assert z[k][:ls].tolist() == list(t[k]), k
+        assert not z[k][ls:].any(), k
+    for k in ("cwu", "cwl"):
+        assert z[k].tolist() == [t[k + "_re"], t[k + "_im"]], k
+
+
+GEO5 = (4, 4, 6, 6)  # Vcb4 = 288: two inverse workgroups with a tail
+LS5 = 5              # odd: non-trivial zMobius sequence tables
+TOL5 = {"double": 1e-11, "single": 1e-4}
+TOL5_EOFA = {"double": 1e-11, "single": 2e-4}
+
+
+def _field5(prec, seed=None):
+    f = SpinorField(LatticeGeometry(GEO5), prec, "cuda", n_parity=1, ls=LS5)
+    return f.gaussian_(seed=seed) if seed is not None else f
+
+
+def _expect5(res, kind, a, x):
+    return a * x + res if kind == 0 else x + a * res
+
+
+def _check5(got, expect, tol, what):
+    err = (got.to_complex()[0] - expect).abs().max().item()
+    print(f"{what}: err {err:.3e} (bound {tol:g})")
+    assert err < tol, (what, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["double", "single"])
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("dagger", [False, True])
+def test_dwf5_xpay_scale_gpu(prec, kind, dagger):
+    a = -0.25
+    inp, x, out = _field5(prec, 401), _field5(prec, 402), _field5(prec)
+    dwf5_op(out, inp, 1.9, -0.55, MF, kind=kind, dagger=dagger, a=a, x=x)
+    fn = ref.dslash5 if kind == 0 else ref.m5inv
+    res = fn(inp.to_complex()[0], LS5, 1.9, -0.55, MF, dagger)
+    _check5(out, _expect5(res, kind, a, x.to_complex()[0]), TOL5[prec],
+            f"dwf5 {prec} kind={kind} dag={dagger}")
+    if kind == 1:  # scale without x
+        dwf5_op(out, inp, 1.9, -0.55, MF, kind=1, dagger=dagger, a=a)
+        _check5(out, a * res, TOL5[prec], f"dwf5 scale {prec} dag={dagger}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["double", "single"])
+@pytest.mark.parametrize("dagger", [False, True])
+def test_dwf5_out_aliases_x_gpu(prec, dagger):
+    """out may alias x in the hop (kind 0): the non-degenerate twisted
+    operators call dwf5_op(out, in, 0, b, -1, kind=0, x=out), and every
+    call without x passes out in x's place. The inverse uses out as its
+    scratch between sweeps, so no operator aliases x there
+    (DiracMobiusPC.M hands it the distinct input field)."""
+    a = -0.25
+    inp, out = _field5(prec, 403), _field5(prec, 404)
+    x0 = out.to_complex()[0].clone()
+    dwf5_op(out, inp, 0.0, 0.7, -1.0, kind=0, dagger=dagger, a=a, x=out)
+    res = ref.dslash5(inp.to_complex()[0], LS5, 0.0, 0.7, -1.0, dagger)
+    _check5(out, a * x0 + res, TOL5[prec], f"dwf5 alias {prec} dag={dagger}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["double", "single"])
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("dagger", [False, True])
+def test_zdwf5_xpay_scale_gpu(prec, kind, dagger):
+    from quda_amd.ops.dispatch import zdwf5_op
+    a = -0.25 + 0.4j
+    diag, hop = _zcoefs_n(LS5)
+    inp, x, out = _field5(prec, 405), _field5(prec, 406), _field5(prec)
+    zdwf5_op(out, inp, diag, hop, MF, kind, dagger=dagger, a=a, x=x)
+    fn = ref.zdslash5 if kind == 0 else ref.zm5inv
+    res = fn(inp.to_complex()[0], LS5, diag, hop, MF, dagger)
+    _check5(out, _expect5(res, kind, a, x.to_complex()[0]), TOL5[prec],
+            f"zdwf5 {prec} kind={kind} dag={dagger}")
+    if kind == 1:
+        zdwf5_op(out, inp, diag, hop, MF, 1, dagger=dagger, a=a)
+        _check5(out, a * res, TOL5[prec], f"zdwf5 scale {prec} dag={dagger}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["double", "single"])
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("dagger", [False, True])
+def test_eofa5_xpay_scale_gpu(setup, prec, kind, dagger):
+    from quda_amd.models import DiracMobiusEofa
+    from quda_amd.ops.dispatch import eofa5_op
+    _, g = setup
+    a = -0.25
+    op = DiracMobiusEofa(g, M5, LS5, mq1=MF, eofa_pm=-1, eofa_shift=-0.21)
+    kw = _eofa_vecs(op)
+    args = (kw["alpha"], kw["beta"], kw["mf"])
+    rank1 = (kw["sh"], kw["pm"], kw["u"], kw["w"])
+    inp, x, out = _field5(prec, 407), _field5(prec, 408), _field5(prec)
+    eofa5_op(out, inp, *args, kind, *rank1, dagger=dagger, a=a, x=x)
+    fn = ref.m5_eofa if kind == 0 else ref.m5inv_eofa
+    res = fn(inp.to_complex()[0], LS5, *args, *rank1, dagger)
+    _check5(out, _expect5(res, kind, a, x.to_complex()[0]), TOL5_EOFA[prec],
+            f"eofa5 {prec} kind={kind} dag={dagger}")
+    if kind == 1:
+        eofa5_op(out, inp, *args, 1, *rank1, dagger=dagger, a=a)
+        _check5(out, a * res, TOL5_EOFA[prec],
+                f"eofa5 scale {prec} dag={dagger}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("swap", [False, True])
+def test_zdwf5_two_tables_two_streams_gpu(swap):
+    """Two coefficient sets launched back to back on two streams with no
+    synchronisation in between: each launch reads its own cached table."""
+    from quda_amd.ops.dispatch import zdwf5_op
+    sets = [_zcoefs_n(LS5), _zcoefs_n(LS5, shift=0.3)]
+    if swap:
+        sets.reverse()
+    inp = _field5("double", 409)
+    outs = [_field5("double"), _field5("double")]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    for (diag, hop), out, st in zip(sets, outs, streams):
+        with torch.cuda.stream(st):
+            zdwf5_op(out, inp, diag, hop, MF, 1)
+    torch.cuda.synchronize()
+    for n, ((diag, hop), out) in enumerate(zip(sets, outs)):
+        res = ref.zm5inv(inp.to_complex()[0], LS5, diag, hop, MF, False)
+        _check5(out, res, TOL5["double"], f"stream {n} swap={swap}")
+
+
+@pytest.mark.gpu
+def test_zdwf5_table_cache_hit_miss_rehit_gpu():
+    from quda_amd.ops.dispatch import zdwf5_op
+    first, other = _zcoefs_n(LS5, shift=0.05), _zcoefs_n(LS5, shift=0.45)
+    inp, out = _field5("double", 410), _field5("double")
+    for n, (diag, hop) in enumerate((first, first, other, first)):
+        out.zero_()
+        zdwf5_op(out, inp, diag, hop, MF, 0, dagger=True)
+        res = ref.zdslash5(inp.to_complex()[0], LS5, diag, hop, MF, True)
+        _check5(out, res, TOL5["double"], f"launch {n}")
+
+
+def _refused(call, out):
+    data = out.data.clone()
+    norm = None if out.norm is None else out.norm.clone()
+    with pytest.raises(RuntimeError):
+        call()
+    torch.cuda.synchronize()
+    assert torch.equal(out.data, data)
+    assert norm is None or torch.equal(out.norm, norm)
+
+
+@pytest.mark.gpu
+def test_5d_refusals_gpu(setup):
+    """No kernel for the precision, or Ls past the tables: the op raises
+    and launches nothing (out stays bitwise as it was)."""
+    from quda_amd.models import DiracMobiusEofa
+    from quda_amd.ops.dispatch import eofa5_op, zdwf5_op
+    geo, g = setup
+    diag, hop = _zcoefs_n(LS5)
+    for prec in ("half", "quarter"):
+        inp, out = _field5(prec, 411), _field5(prec, 412)
+        _refused(lambda: zdwf5_op(out, inp, diag, hop, MF, 0), out)
+        _refused(lambda: zdwf5_op(out, inp, diag, hop, MF, 1), out)
+    kw = _eofa_vecs(DiracMobiusEofa(g, M5, LS5, mq1=MF, eofa_shift=-0.21))
+    inp, out = _field5("quarter", 413), _field5("quarter", 414)
+    for kind in (0, 1):
+        _refused(lambda: eofa5_op(out, inp, kw["alpha"], kw["beta"], kw["mf"],
+                                  kind, kw["sh"], kw["pm"], kw["u"], kw["w"]),
+                 out)
+    # Ls = 33 > QA_ZMAX
+    inp = SpinorField(geo, "single", "cuda", n_parity=1, ls=33).gaussian_(seed=415)
+    out = SpinorField(geo, "single", "cuda", n_parity=1, ls=33).gaussian_(seed=416)
+    diag, hop = _zcoefs_n(33)
+    kw = _eofa_vecs(DiracMobiusEofa(g, M5, 33, mq1=MF, eofa_shift=-0.21))
+    _refused(lambda: zdwf5_op(out, inp, diag, hop, MF, 0), out)
+    for kind in (0, 1):
+        _refused(lambda: eofa5_op(out, inp, kw["alpha"], kw["beta"], kw["mf"],
+                                  kind, kw["sh"], kw["pm"], kw["u"], kw["w"]),
+                 out)
+    # the binding's own Ls check, behind the Python one
+    from quda_amd.ops.dispatch import _zpack, _ztables, hip_ext, norm_or_empty
+    table = _zpack(_ztables(LS5, *_zcoefs_n(LS5), MF, False), LS5)
+    _refused(lambda: hip_ext().zdwf5(
+        out.data, norm_or_empty(out), inp.data, norm_or_empty(inp), out.data,
+        norm_or_empty(out), geo.volume_cb, 33, False, 1.0, 0.0, 0, table), out)
