@@ -30,6 +30,7 @@ KERNEL_SOURCES = [
     "dslash_wilson_h.hip",
     "dslash_wilson_q.hip",
     "dslash_staggered.hip",
+    "laplace.hip",
     "dslash_dwf.hip",
     "dslash_dwf_fused.hip",
     "dslash_wilson_mrhs.hip",

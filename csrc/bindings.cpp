@@ -298,6 +298,51 @@ static void dslash_staggered(at::Tensor out, at::Tensor out_n, at::Tensor in,
   check_launch("dslash_staggered");
 }
 
+// covariant hop sum on full-parity fields (csrc/laplace.h)
+static void laplace(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                    at::Tensor in_n, at::Tensor gauge,
+                    std::vector<int64_t> dims, int64_t parity_offset,
+                    int64_t Vcb, int64_t hops, int64_t shift, double a,
+                    double b, int64_t recon, int64_t nspin, int64_t cpt,
+                    bool nbr_link) {
+  TORCH_CHECK(out.is_contiguous() && in.is_contiguous() && gauge.is_contiguous());
+  TORCH_CHECK(hops >= 0 && hops < 256, "laplace: hops is an 8-bit mask");
+  TORCH_CHECK(recon == 18 || recon == 12, "laplace: recon 18 or 12");
+  TORCH_CHECK(nspin == 4 || nspin == 1, "laplace: nspin 4 or 1");
+  LaplaceCall c{};
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  TORCH_CHECK(Vcb > 0 && dims[0] % 2 == 0 &&
+                  dims[0] * dims[1] * dims[2] * dims[3] == 2 * Vcb,
+              "laplace: dims do not match the cb volume");
+  for (int mu = 0; mu < 4; ++mu)
+    TORCH_CHECK(dims[mu] >= 2, "laplace: local extents of at least 2");
+  TORCH_CHECK(out.numel() == 2 * Vcb * 6 * nspin &&
+                  in.numel() == out.numel() &&
+                  gauge.numel() == 2 * 8 * recon * Vcb,
+              "laplace: full-parity fields of this lattice expected");
+  TORCH_CHECK(in.scalar_type() == out.scalar_type() &&
+                  gauge.scalar_type() == out.scalar_type(),
+              "laplace: one precision for all fields");
+  c.prec = prec_of(out);
+  if (c.prec == 2)
+    TORCH_CHECK(out_n.numel() == 2 * Vcb && in_n.numel() == 2 * Vcb,
+                "laplace: half fields carry a norm per site");
+  c.out = field_of(out, out_n, Vcb);
+  c.in = field_of(in, in_n, Vcb);
+  c.gauge = gauge.data_ptr();
+  c.hops = (int)hops;
+  c.shift = (int)shift;
+  c.a = a;
+  c.b = b;
+  c.recon = (int)recon;
+  c.nspin = (int)nspin;
+  c.cpt = (int)cpt;
+  c.nbr_link = nbr_link;
+  TORCH_CHECK(launch_laplace(c, stream()),
+              "laplace: no kernel for this call");
+  check_launch("laplace");
+}
+
 static at::Tensor blas_op(int64_t op, double a, double b, at::Tensor x,
                           at::Tensor x_n, at::Tensor y, at::Tensor y_n,
                           int64_t Vcb, int64_t sites, double c2 = 0.0,
@@ -1070,6 +1115,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("coarse_dslash_mfma", &coarse_dslash_mfma,
         "coarse-grid 9-matrix dslash on f32 MFMA tiles");
   m.def("dslash_staggered", &dslash_staggered, "naive staggered dslash");
+  m.def("laplace", &laplace,
+        "out = a * sum of the masked covariant hops of in + b * in");
   m.def("set_dslash_block", &set_dslash_block, "autotuner: dslash workgroup size");
   m.def("set_dslash_waves", &set_dslash_waves,
         "occupancy experiment: 0 default, 3 = 64-thread/3-wave variant "

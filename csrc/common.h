@@ -234,6 +234,26 @@ struct SpinorAcc {
       store_chunk<S, W>(data + base + (long)ch * V * W, tmp + ch * W);
   }
 
+  // column range: the N chunks [c0, c0 + N) of site g, raw (a colour
+  // 3-vector of one spin is 6 reals). Whole-site ranges only where the
+  // precision carries a per-site norm.
+  template <int N>
+  __device__ __forceinline__ void load_chunks(S *tmp, long g, int c0) const {
+    long base = chunk_base(g) + (long)c0 * V * W;
+#pragma unroll
+    for (int ch = 0; ch < N; ++ch)
+      load_chunk<S, W>(data + base + (long)ch * V * W, tmp + ch * W);
+  }
+  template <int N>
+  __device__ __forceinline__ void store_chunks(const S *tmp, long g,
+                                               int c0) const {
+    static_assert(!Prec::has_norm || N == NCH, "normed sites store whole");
+    long base = chunk_base(g) + (long)c0 * V * W;
+#pragma unroll
+    for (int ch = 0; ch < N; ++ch)
+      store_chunk<S, W>(data + base + (long)ch * V * W, tmp + ch * W);
+  }
+
   // [4][3]-shaped views for the Wilson kernels (NCOMP == 24 only)
   __device__ __forceinline__ void load_g(cplx<R> (&out)[4][3], long g) const {
     static_assert(NCOMP == 24);

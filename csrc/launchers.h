@@ -232,6 +232,27 @@ void launch_dslash_staggered(const StagDslashCall &c, hipStream_t st);
 void launch_pack_face_stag(const PackCall &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// covariant hop sum on full-parity fields (csrc/laplace.h):
+//   out = a * sum_{h in hops} T_h in + b * in
+#define QA_LAP_CPT_DOUBLE 2  // default columns per thread, nspin 4
+#define QA_LAP_CPT_SINGLE 2
+struct LaplaceCall {
+  BlasField out, in;  // full-parity fields (Vcb = cb volume); never alias
+  const void *gauge;  // stencil layout, both parity blocks
+  LatDesc lat;
+  int hops;           // bit mu: +mu hop, bit 4+mu: -mu hop
+  int shift;          // hop distance = the gauge field's shift, 1 or 2
+  double a, b;
+  int recon;          // 18 or 12
+  int prec;           // 0 double, 1 single, 2 half
+  int nspin;          // 4 or 1
+  int cpt;            // columns per thread; 0 = the precision's default
+  bool nbr_link;      // backward link from the neighbour's forward slot
+};
+// false, and nothing launched, when the call has no instantiation
+bool launch_laplace(const LaplaceCall &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // 5th-dimension family (csrc/dslash_dwf.h): Moebius, zMobius and EOFA share
 // one call base. Each launcher returns false, and launches nothing, when
 // the precision has no instantiation or a table could not be staged.

@@ -10,6 +10,7 @@ import torch
 from ..fields.gauge import GaugeField
 from ..fields.geometry import LatticeGeometry, checkerboard_join, checkerboard_split
 from ..fields.spinor import SpinorField
+from ..ops import dispatch
 
 
 def spin_taste_phase(geo: LatticeGeometry, kind: str) -> torch.Tensor:
@@ -45,12 +46,17 @@ def apply_spin_taste(psi: SpinorField, kind: str) -> SpinorField:
 
 
 def two_link_laplace(two: GaugeField, psi: SpinorField, out: SpinorField,
-                     *, a: float, b: float) -> SpinorField:
+                     *, a: float, b: float, native=None) -> SpinorField:
     """out = a * Lap2 psi + b * psi with the TWO-LINK spatial Laplacian
     Lap2 psi(x) = sum_{i<3}[N_i(x) psi(x+2i) + N_i(x-2i)^d psi(x-2i)]
     - 6 psi, N_i = U_i(x) U_i(x+i) (pass `two` as a shift=2-style field
-    built by two_links)."""
+    built by two_links). Given a GaugeField(shift=2) of the two-links, the
+    HIP hop-sum kernel serves the call under the flag of
+    models.laplace.laplace_apply."""
     geo = psi.geo
+    if (isinstance(two, GaugeField) and two.shift == 2
+            and dispatch.laplace_eligible(out, psi, two, native)):
+        return dispatch.laplace_hops(out, psi, two, 0x77, a, b - 6.0 * a)
     u = two.to_complex()
     lo = geo.lex_of_cb.to(psi.device)
     U = torch.empty((4, geo.volume, 3, 3), dtype=u.dtype, device=u.device)
@@ -94,18 +100,29 @@ def two_links(u: torch.Tensor, geo: LatticeGeometry) -> torch.Tensor:
 
 def gaussian_smear_two_link(u: torch.Tensor, geo: LatticeGeometry,
                             psi: SpinorField, *, width: float,
-                            n_steps: int) -> SpinorField:
+                            n_steps: int, native=None) -> SpinorField:
     """Staggered Gaussian smearing with two-link transport
     (ref: performTwoLinkGaussianSmearNStep):
-    psi <- [(1 + w Lap2/(4 n)) ]^n psi with w = width^2."""
+    psi <- [(1 + w Lap2/(4 n)) ]^n psi with w = width^2.
+    native: see models.laplace.laplace_apply; the native path packs the
+    two-links once into a shift-2 stencil field at psi's precision."""
+    from .laplace import _native_on, hop_pingpong
     N = two_links(u, geo)
+    coef = width * width / (4.0 * n_steps)
+    if (_native_on(native) and psi.device.type == "cuda"
+            and psi.precision in ("double", "single", "half")):
+        two = GaugeField(geo, psi.precision, psi.device,
+                         shift=2).from_complex(N.to(psi.device))
+        res = hop_pingpong(two, psi, 0x77, coef, 1.0 - 6.0 * coef, n_steps,
+                           True)
+        if res is not None:
+            return res
 
     class _Wrap:  # two_link_laplace only reads .to_complex()
         def to_complex(self_inner):
             return N
 
     two = _Wrap()
-    coef = width * width / (4.0 * n_steps)
     cur = psi
     for _ in range(n_steps):
         nxt = psi.clone_empty()

@@ -1118,3 +1118,60 @@ def galerkin_build(V: torch.Tensor, nbr_ab: torch.Tensor, bnd: torch.Tensor,
     hip_ext().galerkin_build(X, Y, scratch, V, nbr_ab, bnd, link_ab, clov_ab,
                              coef)
     return X, Y
+
+
+# ---------------------------------------------------------------------------
+# covariant hop sum on full-parity fields (csrc/laplace.h): the kernel under
+# laplace_apply, covdev_apply, wuppertal_smear, GaugeLaplace and the two-link
+# smear. Opt-in: QUDA_AMD_NATIVE_LAPLACE=1 or native=True.
+# ---------------------------------------------------------------------------
+
+def native_laplace_default() -> bool:
+    """QUDA_AMD_NATIVE_LAPLACE=1 opts into the HIP hop-sum kernel (default
+    off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_LAPLACE", "0") == "1"
+
+
+def laplace_eligible(out: SpinorField, inp: SpinorField, gauge: GaugeField,
+                     native=None) -> bool:
+    """True when laplace_hops may serve the call: the flag is on (native, or
+    the environment when native is None), all fields on the GPU, one
+    precision of double/single/half, recon none or twelve, full-parity 4-d
+    fields of nspin 4 or 1, a gauge shift of 1 or 2, a single-rank lattice,
+    and out not aliasing inp. Everything else, an explicit native=True
+    included, takes the torch path unchanged."""
+    from ..parallel import comms
+    if not (native_laplace_default() if native is None else bool(native)):
+        return False
+    if not all(f.device.type == "cuda" for f in (out, inp, gauge)):
+        return False
+    return bool(
+        out.precision == inp.precision == gauge.precision
+        and out.precision in ("double", "single", "half")
+        and gauge.reconstruct in ("none", "twelve")
+        and out.n_parity == 2 and inp.n_parity == 2
+        and out.nspin == inp.nspin and out.nspin in (4, 1)
+        and out.ls == 1 and inp.ls == 1
+        and gauge.shift in (1, 2)
+        and comms.comm_mask() == 0
+        and out is not inp and out.data.data_ptr() != inp.data.data_ptr())
+
+
+def laplace_hops(out: SpinorField, inp: SpinorField, gauge: GaugeField,
+                 hops: int, a: float, b: float, cpt: int = 0,
+                 nbr_link: bool = False) -> SpinorField:
+    """out = a * sum_{h in hops} T_h inp + b * inp in one launch over both
+    parities; bit mu of hops is the +mu hop U_mu(x) inp(x + H mu), bit 4+mu
+    the -mu hop U_mu(x - H mu)^d inp(x - H mu), H = gauge.shift. The caller
+    has checked laplace_eligible. cpt (columns per thread, 0 = default) and
+    nbr_link (backward link from the neighbour's forward slot, H = 1) pick
+    the measured variants of profiles/r11_laplace.md."""
+    geo = inp.geo
+    hip_ext().laplace(
+        out.data, norm_or_empty(out), inp.data, norm_or_empty(inp),
+        gauge.data, list(geo.dims), geo.parity_offset, geo.volume_cb,
+        int(hops), int(gauge.shift), float(a), float(b),
+        RECON_COMPS[gauge.reconstruct], inp.nspin, int(cpt), bool(nbr_link))
+    trace_record("laplace", f"{inp.precision}/ns{inp.nspin}/h{hops:#04x}")
+    return out
