@@ -343,6 +343,135 @@ static void laplace(at::Tensor out, at::Tensor out_n, at::Tensor in,
   check_launch("laplace");
 }
 
+// contraction family (csrc/contract.h): full-parity nspin-4 fields x, y
+static ContractCall contract_call(const char *what, const at::Tensor &x,
+                                  const at::Tensor &x_n, const at::Tensor &y,
+                                  const at::Tensor &y_n,
+                                  const std::vector<int64_t> &dims,
+                                  int64_t parity_offset, int64_t Vcb,
+                                  const std::vector<int64_t> &gamma) {
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.is_contiguous() &&
+                  y.is_contiguous(), what, ": contiguous GPU fields");
+  ContractCall c{};
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  TORCH_CHECK(Vcb > 0 && dims[0] % 2 == 0 && dims[1] > 0 && dims[2] > 0 &&
+                  dims[3] > 0 &&
+                  dims[0] * dims[1] * dims[2] * dims[3] == 2 * Vcb,
+              what, ": dims do not match the cb volume");
+  TORCH_CHECK(x.numel() == 2 * Vcb * 24 && y.numel() == x.numel() &&
+                  x.scalar_type() == y.scalar_type(),
+              what, ": two full-parity nspin-4 fields of one precision");
+  c.prec = prec_of(x);
+  TORCH_CHECK(c.prec <= 2, what, ": double, single or half");
+  if (c.prec == 2)
+    TORCH_CHECK(x_n.numel() == 2 * Vcb && y_n.numel() == 2 * Vcb &&
+                    x_n.is_cuda() && y_n.is_cuda(),
+                what, ": half fields carry a norm per site");
+  c.x = field_of(x, x_n, Vcb);
+  c.y = field_of(y, y_n, Vcb);
+  TORCH_CHECK(gamma.size() == 16, what, ": 16 gamma-table words");
+  for (int g = 0; g < 16; ++g) c.gamma[g] = (unsigned)gamma[g] & 0xffffu;
+  return c;
+}
+
+static at::Tensor contract_site(at::Tensor x, at::Tensor x_n, at::Tensor y,
+                                at::Tensor y_n, std::vector<int64_t> dims,
+                                int64_t parity_offset, int64_t Vcb,
+                                std::vector<int64_t> gamma, bool dr) {
+  ContractCall c = contract_call("contract_site", x, x_n, y, y_n, dims,
+                                 parity_offset, Vcb, gamma);
+  auto out = at::empty({2 * Vcb, 16}, x.options().dtype(at::kComplexDouble));
+  c.out = out.data_ptr();
+  c.dr = dr;
+  TORCH_CHECK(launch_contract_site(c, stream()),
+              "contract_site: no kernel for this call");
+  check_launch("contract_site");
+  return out;
+}
+
+// partial [tiles][n_mom][L][16]; phases: CPU complex128 [n_mom][sum of the
+// extents other than reduct_dim]
+static at::Tensor contract_slices(at::Tensor x, at::Tensor x_n, at::Tensor y,
+                                  at::Tensor y_n, std::vector<int64_t> dims,
+                                  int64_t parity_offset, int64_t Vcb,
+                                  std::vector<int64_t> gamma,
+                                  at::Tensor phases, int64_t reduct_dim,
+                                  int64_t ns) {
+  ContractCall c = contract_call("contract_slices", x, x_n, y, y_n, dims,
+                                 parity_offset, Vcb, gamma);
+  TORCH_CHECK(reduct_dim >= 0 && reduct_dim < 4, "contract_slices: reduct_dim");
+  TORCH_CHECK(ns == 0 || ns == 128 || ns == 256, "contract_slices: ns");
+  int64_t ltot = dims[0] + dims[1] + dims[2] + dims[3] - dims[reduct_dim];
+  TORCH_CHECK(phases.is_cpu() && phases.is_contiguous() &&
+                  phases.scalar_type() == at::kComplexDouble &&
+                  phases.dim() == 2 && phases.size(0) >= 1 &&
+                  phases.size(1) == ltot,
+              "contract_slices: phases is CPU complex128 [n_mom][", ltot, "]");
+  c.reduct_dim = (int)reduct_dim;
+  c.phases = phases.data_ptr();
+  c.n_mom = (int)phases.size(0);
+  c.ns = (int)ns;
+  auto out = at::empty({contract_slice_tiles(c.lat, c.reduct_dim, c.ns),
+                        c.n_mom, dims[reduct_dim], 16},
+                       x.options().dtype(at::kComplexDouble));
+  c.out = out.data_ptr();
+  TORCH_CHECK(launch_contract_slices(c, stream()),
+              "contract_slices: no kernel for this call");
+  check_launch("contract_slices");
+  return out;
+}
+
+// partial [tiles][n_ev][L][4]
+static at::Tensor evec_project(std::vector<at::Tensor> evecs,
+                               std::vector<at::Tensor> evec_norms,
+                               at::Tensor psi, at::Tensor psi_n,
+                               std::vector<int64_t> dims,
+                               int64_t parity_offset, int64_t Vcb,
+                               int64_t reduct_dim, int64_t ne) {
+  TORCH_CHECK(psi.is_cuda() && psi.is_contiguous() &&
+                  psi.numel() == 2 * Vcb * 24,
+              "evec_project: psi is a full-parity nspin-4 GPU field");
+  TORCH_CHECK(reduct_dim >= 0 && reduct_dim < 4, "evec_project: reduct_dim");
+  TORCH_CHECK(ne == 0 || ne == 4 || ne == 8, "evec_project: ne");
+  TORCH_CHECK(!evecs.empty() && evecs.size() == evec_norms.size(),
+              "evec_project: one norm tensor per eigenvector");
+  EvecProjectCall c{};
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  TORCH_CHECK(Vcb > 0 && dims[0] % 2 == 0 && dims[1] > 0 && dims[2] > 0 &&
+                  dims[3] > 0 &&
+                  dims[0] * dims[1] * dims[2] * dims[3] == 2 * Vcb,
+              "evec_project: dims do not match the cb volume");
+  c.prec = prec_of(psi);
+  TORCH_CHECK(c.prec <= 2, "evec_project: double, single or half");
+  if (c.prec == 2)
+    TORCH_CHECK(psi_n.numel() == 2 * Vcb && psi_n.is_cuda(),
+                "evec_project: half fields carry a norm per site");
+  c.psi = field_of(psi, psi_n, Vcb);
+  std::vector<BlasField> ev;
+  for (size_t i = 0; i < evecs.size(); ++i) {
+    const at::Tensor &v = evecs[i], &n = evec_norms[i];
+    TORCH_CHECK(v.is_cuda() && v.is_contiguous() && v.numel() == 2 * Vcb * 6 &&
+                    v.scalar_type() == psi.scalar_type(),
+                "evec_project: full-parity nspin-1 GPU fields of psi's precision");
+    if (c.prec == 2)
+      TORCH_CHECK(n.numel() == 2 * Vcb && n.is_cuda(),
+                  "evec_project: half fields carry a norm per site");
+    ev.push_back(field_of(v, n, Vcb));
+  }
+  c.evecs = ev.data();
+  c.n_ev = (int)ev.size();
+  c.reduct_dim = (int)reduct_dim;
+  c.ne = (int)ne;
+  auto out = at::empty({evec_project_tiles(c.lat, c.reduct_dim), c.n_ev,
+                        dims[reduct_dim], 4},
+                       psi.options().dtype(at::kComplexDouble));
+  c.out = out.data_ptr();
+  TORCH_CHECK(launch_evec_project(c, stream()),
+              "evec_project: no kernel for this call");
+  check_launch("evec_project");
+  return out;
+}
+
 static at::Tensor blas_op(int64_t op, double a, double b, at::Tensor x,
                           at::Tensor x_n, at::Tensor y, at::Tensor y_n,
                           int64_t Vcb, int64_t sites, double c2 = 0.0,
@@ -1117,6 +1246,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dslash_staggered", &dslash_staggered, "naive staggered dslash");
   m.def("laplace", &laplace,
         "out = a * sum of the masked covariant hops of in + b * in");
+  m.def("contract_site", &contract_site,
+        "per-site open-spin matrix or 16 gamma traces at the lex index");
+  m.def("contract_slices", &contract_slices,
+        "per-tile momentum-projected slice sums of the 16 gamma traces");
+  m.def("evec_project", &evec_project,
+        "per-tile slice sums of <evec_i | psi> per spin");
   m.def("set_dslash_block", &set_dslash_block, "autotuner: dslash workgroup size");
   m.def("set_dslash_waves", &set_dslash_waves,
         "occupancy experiment: 0 default, 3 = 64-thread/3-wave variant "

@@ -253,6 +253,40 @@ struct LaplaceCall {
 bool launch_laplace(const LaplaceCall &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// contraction family on full-parity nspin-4 fields (csrc/contract.h). Each
+// launcher returns false, and launches nothing, when the call has no
+// instantiation or a table could not be staged.
+#define QA_CT_NS 128  // default sites per tile of the slice-sum kernel (measured)
+#define QA_CT_NE 8    // default eigenvectors per launch of the projection
+struct ContractCall {
+  BlasField x, y;       // Vcb = cb volume
+  LatDesc lat;
+  int prec;             // 0 double, 1 single, 2 half
+  unsigned gamma[16];   // word g: nibble t = col | phase code << 2 of row t
+  void *out;            // site: [V][16]; slices: [tiles][n_mom][L][16] complex
+  int dr;               // site kernel: 1 = gamma traces, 0 = open spin
+  int reduct_dim;       // slices
+  const void *phases;   // host complex double [n_mom][sum of the other dims]
+  int n_mom;
+  int ns;               // sites per tile, 128 or 256; 0 = QA_CT_NS
+};
+struct EvecProjectCall {
+  BlasField psi;           // nspin 4
+  const BlasField *evecs;  // n_ev nspin-1 fields of psi's precision
+  int n_ev;
+  LatDesc lat;
+  int prec;
+  void *out;               // [tiles][n_ev][L][4] complex double
+  int reduct_dim;
+  int ne;                  // eigenvectors per launch, 4 or 8; 0 = QA_CT_NE
+};
+long contract_slice_tiles(const LatDesc &l, int reduct_dim, int ns);
+long evec_project_tiles(const LatDesc &l, int reduct_dim);
+bool launch_contract_site(const ContractCall &c, hipStream_t st);
+bool launch_contract_slices(const ContractCall &c, hipStream_t st);
+bool launch_evec_project(const EvecProjectCall &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // 5th-dimension family (csrc/dslash_dwf.h): Moebius, zMobius and EOFA share
 // one call base. Each launcher returns false, and launches nothing, when
 // the precision has no instantiation or a table could not be staged.

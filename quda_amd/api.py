@@ -828,23 +828,23 @@ def compute_clover_force_quda(kappa: float, csw: float, x_sol: torch.Tensor,
 
 
 def contract_quda(x: torch.Tensor, y: torch.Tensor, p: InvertParam,
-                  mode: str = "open") -> torch.Tensor:
+                  mode: str = "open", native=None) -> torch.Tensor:
     """ref: contractQuda — open-spin / DeGrand-Rossi contraction of two
-    propagator fields."""
+    propagator fields. native: see ops.contract.contract_open_spin."""
     from .ops import contract
     xf = _wrap(x, p, 2)
     yf = _wrap(y, p, 2)
     if mode == "open":
-        return contract.contract_open_spin(xf, yf)
-    return contract.contract_dr(xf, yf)
+        return contract.contract_open_spin(xf, yf, native=native)
+    return contract.contract_dr(xf, yf, native=native)
 
 
 def contract_ft_quda(x: torch.Tensor, y: torch.Tensor, p: InvertParam,
-                     momenta, reduct_dim: int = 3) -> torch.Tensor:
+                     momenta, reduct_dim: int = 3, native=None) -> torch.Tensor:
     """ref: contractFTQuda — momentum-projected timeslice contraction."""
     from .ops import contract
     return contract.contract_ft(_wrap(x, p, 2), _wrap(y, p, 2),
-                                list(momenta), reduct_dim)
+                                list(momenta), reduct_dim, native=native)
 
 
 def new_deflation_quda(p: InvertParam, e: EigParam):

@@ -527,7 +527,7 @@ def qudaFreeTwoLink() -> None:
 
 
 def qudaContractFT(x_milc: torch.Tensor, y_milc: torch.Tensor, momenta,
-                   kappa: float = 0.1):
+                   kappa: float = 0.1, native=None):
     """Momentum-projected timeslice contraction of two Wilson propagator
     fields in MILC (lex) order (ref qudaContractFT -> contractFTQuda)."""
     from ..fields.geometry import checkerboard_split
@@ -535,7 +535,7 @@ def qudaContractFT(x_milc: torch.Tensor, y_milc: torch.Tensor, momenta,
     p = api.InvertParam(dslash_type=api.DslashType.WILSON, kappa=kappa)
     xs = checkerboard_split(x_milc.reshape(geo.volume, 4, 3), geo)
     ys = checkerboard_split(y_milc.reshape(geo.volume, 4, 3), geo)
-    return api.contract_ft_quda(xs, ys, p, momenta)
+    return api.contract_ft_quda(xs, ys, p, momenta, native=native)
 
 
 # ---------------------------------------------------------------------------

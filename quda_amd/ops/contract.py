@@ -5,6 +5,7 @@ re-derived; einsum/batched-GEMM shaped, torch dispatches to rocBLAS)."""
 
 from __future__ import annotations
 
+import functools
 from typing import List, Optional
 
 import numpy as np
@@ -15,21 +16,32 @@ from ..fields.geometry import LatticeGeometry, checkerboard_join
 from ..fields.spinor import SpinorField
 
 
-def contract_open_spin(x: SpinorField, y: SpinorField) -> torch.Tensor:
+def contract_open_spin(x: SpinorField, y: SpinorField,
+                       native=None) -> torch.Tensor:
     """Open-spin color-contracted bilinear per site:
     C[x, s, s'] = sum_c conj(x(s,c)) y(s',c)  ->  [V, 4, 4] (lex order)
-    (ref: contractQuda QUDA_CONTRACT_TYPE_OPEN)."""
+    (ref: contractQuda QUDA_CONTRACT_TYPE_OPEN). native (None: the
+    QUDA_AMD_NATIVE_CONTRACT switch) asks for the HIP kernels of
+    csrc/contract.h, here and below, where dispatch.contract_eligible
+    holds; every other call runs the torch code."""
+    from . import dispatch
+    if dispatch.contract_eligible((x, y), native):
+        return dispatch.contract_site(x, y, gamma_table(), False).view(
+            -1, 4, 4)
     geo = x.geo
     xc = checkerboard_join(x.to_complex(), geo)
     yc = checkerboard_join(y.to_complex(), geo)
     return torch.einsum("vsc,vtc->vst", xc.conj(), yc)
 
 
-def contract_dr(x: SpinorField, y: SpinorField) -> torch.Tensor:
+def contract_dr(x: SpinorField, y: SpinorField, native=None) -> torch.Tensor:
     """Gamma-insertion contraction: tr_spin[ G_i^dag X^dag G_i Y ] summed
     over color, for the 16 DeGrand-Rossi gamma-basis elements
     -> [V, 16] (ref: QUDA_CONTRACT_TYPE_DR)."""
-    C = contract_open_spin(x, y)  # [V,4,4]
+    from . import dispatch
+    if dispatch.contract_eligible((x, y), native):
+        return dispatch.contract_site(x, y, gamma_table(), True)
+    C = contract_open_spin(x, y, native=False)  # [V,4,4]
     dev, dt = C.device, C.dtype
     gammas = _gamma_basis(dev, dt)
     # tr[ G^d C^T_spin? ] — standard: sum_{s,s'} G[s',s] C[s,s']
@@ -49,12 +61,53 @@ def _gamma_basis(device, dtype):
     return torch.tensor(np.stack(mats), device=device, dtype=dtype)
 
 
+@functools.lru_cache(maxsize=None)
+def gamma_table() -> tuple:
+    """The 16 matrices of _gamma_basis as the table the HIP kernels take:
+    word g holds, in nibble t, col | k << 2 of the one non-zero entry i^k of
+    row t of G_g, so that D[g] = sum_t i^k C[col, t]. Raises if a matrix is
+    not monomial with entries in {1, i, -1, -i}."""
+    units = [1, 1j, -1, -1j]
+    words = []
+    for g, G in enumerate(_gamma_basis("cpu", torch.complex128).numpy()):
+        w = 0
+        for t in range(4):
+            cols = np.flatnonzero(G[t])
+            if len(cols) != 1 or G[t, cols[0]] not in units:
+                raise ValueError(f"gamma basis element {g} is not monomial "
+                                 f"with unit entries: row {t} = {G[t]}")
+            w |= (int(cols[0]) | units.index(G[t, cols[0]]) << 2) << (4 * t)
+        words.append(w)
+    return tuple(words)
+
+
+def phase_table(dims, momenta, reduct_dim: int) -> torch.Tensor:
+    """The separable factors of e^{-i p.x}, CPU complex128 [n_mom, sum of the
+    extents other than reduct_dim]: for each momentum the rows
+    exp(-i 2 pi p_d x_d / L_d), x_d = 0..L_d-1, of the dimensions
+    d != reduct_dim in ascending order."""
+    rows = []
+    for p in momenta:
+        rows.append(torch.cat([
+            torch.exp(-1j * (2 * np.pi * p[d]
+                             * torch.arange(dims[d], dtype=torch.float64)
+                             / dims[d]))
+            for d in range(4) if d != reduct_dim]))
+    return torch.stack(rows).to(torch.complex128).contiguous()
+
+
 def contract_ft(x: SpinorField, y: SpinorField, momenta: List[tuple],
-                reduct_dim: int = 3) -> torch.Tensor:
+                reduct_dim: int = 3, native=None) -> torch.Tensor:
     """Momentum-projected timeslice contraction (ref: contractFTQuda):
     C[p, t, g] = sum_{vec x} e^{-i p.x} tr[...] -> [n_mom, T, 16]."""
+    from . import dispatch
+    if len(momenta) and dispatch.contract_eligible((x, y), native, reduct_dim):
+        from ..parallel.comms import allreduce_tensor
+        return allreduce_tensor(dispatch.contract_slices(
+            x, y, gamma_table(),
+            phase_table(x.geo.dims, momenta, reduct_dim), reduct_dim))
     geo = x.geo
-    c = contract_dr(x, y)  # [V, 16] lex
+    c = contract_dr(x, y, native=False)  # [V, 16] lex
     coords = geo.coords.to(torch.float64)
     dims = geo.dims
     out = torch.empty((len(momenta), dims[reduct_dim], 16),
@@ -74,10 +127,16 @@ def contract_ft(x: SpinorField, y: SpinorField, momenta: List[tuple],
 
 
 def evec_project(evecs: List[SpinorField], psi: SpinorField,
-                 reduct_dim: int = 3) -> torch.Tensor:
+                 reduct_dim: int = 3, native=None) -> torch.Tensor:
     """LapH sink projection <evec_i | psi> per timeslice and spin
     -> [n_ev, T, 4] (ref: lib/evec_project.cu; evecs are nspin=1 laplace
     eigenvectors, psi a 4-spin propagator field)."""
+    from . import dispatch
+    if len(evecs) and dispatch.contract_eligible((psi,), native, reduct_dim,
+                                                 evecs):
+        from ..parallel.comms import allreduce_tensor
+        return allreduce_tensor(dispatch.evec_project_slices(
+            evecs, psi, reduct_dim))
     geo = psi.geo
     T = geo.dims[reduct_dim]
     tcoord = geo.coords[:, reduct_dim].to(torch.int64)

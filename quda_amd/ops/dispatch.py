@@ -1175,3 +1175,90 @@ def laplace_hops(out: SpinorField, inp: SpinorField, gauge: GaugeField,
         RECON_COMPS[gauge.reconstruct], inp.nspin, int(cpt), bool(nbr_link))
     trace_record("laplace", f"{inp.precision}/ns{inp.nspin}/h{hops:#04x}")
     return out
+
+
+# ---------------------------------------------------------------------------
+# contraction family (csrc/contract.h): per-site contraction, momentum slice
+# sums and the eigenvector sink projection under ops/contract.py. Opt-in:
+# QUDA_AMD_NATIVE_CONTRACT=1 or native=True.
+# ---------------------------------------------------------------------------
+
+def native_contract_default() -> bool:
+    """QUDA_AMD_NATIVE_CONTRACT=1 opts into the HIP contraction kernels
+    (default off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_CONTRACT", "0") == "1"
+
+
+def contract_eligible(fields, native=None, reduct_dim: int = 3,
+                      evecs=()) -> bool:
+    """True when the contraction kernels may serve the call: the flag is on
+    (native, or the environment when native is None), every field on the GPU
+    and of one precision of double/single/half, full-parity 4-d fields of
+    nspin 4 (evecs: nspin 1), a single-rank lattice and 0 <= reduct_dim < 4.
+    Everything else, an explicit native=True included, takes the torch path
+    unchanged."""
+    from ..parallel import comms
+    if not (native_contract_default() if native is None else bool(native)):
+        return False
+    every = list(fields) + list(evecs)
+    if not all(f.device.type == "cuda" for f in every):
+        return False
+    prec = every[0].precision
+    return bool(
+        prec in ("double", "single", "half")
+        and all(f.precision == prec and f.n_parity == 2 and f.ls == 1
+                for f in every)
+        and all(f.nspin == 4 for f in fields)
+        and all(f.nspin == 1 for f in evecs)
+        and comms.comm_mask() == 0
+        and 0 <= reduct_dim < 4)
+
+
+def _contract_args(x: SpinorField, y: SpinorField, gamma_words):
+    geo = x.geo
+    return (x.data, norm_or_empty(x), y.data, norm_or_empty(y),
+            list(geo.dims), geo.parity_offset, geo.volume_cb,
+            list(gamma_words))
+
+
+def contract_site(x: SpinorField, y: SpinorField, gamma_words,
+                  dr: bool) -> torch.Tensor:
+    """[V, 16] complex128 at the lexicographic site index: the open-spin
+    matrix C[s, t] (entry 4 s + t), or with dr its 16 gamma traces.
+    gamma_words is contract.gamma_table(). The caller has checked
+    contract_eligible."""
+    out = hip_ext().contract_site(*_contract_args(x, y, gamma_words),
+                                  bool(dr))
+    trace_record("contract_site",
+                 f"{x.precision}/{'dr' if dr else 'open'}")
+    return out
+
+
+def contract_slices(x: SpinorField, y: SpinorField, gamma_words,
+                    phases: torch.Tensor, reduct_dim: int,
+                    ns: int = 0) -> torch.Tensor:
+    """[n_mom, L, 16] complex128: the gamma traces times the momentum phases
+    summed over each slice of reduct_dim. phases is contract.phase_table();
+    the per-tile partial sums are added in tile order. ns (sites per tile,
+    0 = default) picks the measured variants of profiles/r12_contract.md."""
+    part = hip_ext().contract_slices(*_contract_args(x, y, gamma_words),
+                                     phases, int(reduct_dim), int(ns))
+    trace_record("contract_slices",
+                 f"{x.precision}/rd{reduct_dim}/p{phases.shape[0]}")
+    return torch.sum(part, dim=0)
+
+
+def evec_project_slices(evecs, psi: SpinorField, reduct_dim: int,
+                        ne: int = 0) -> torch.Tensor:
+    """[n_ev, L, 4] complex128: <evec_i | psi> per spin, summed over each
+    slice of reduct_dim; psi is read once per batch of ne eigenvectors
+    (0 = default)."""
+    geo = psi.geo
+    part = hip_ext().evec_project(
+        [v.data for v in evecs], [norm_or_empty(v) for v in evecs],
+        psi.data, norm_or_empty(psi), list(geo.dims), geo.parity_offset,
+        geo.volume_cb, int(reduct_dim), int(ne))
+    trace_record("evec_project",
+                 f"{psi.precision}/rd{reduct_dim}/n{len(evecs)}")
+    return torch.sum(part, dim=0)
