@@ -32,6 +32,7 @@ KERNEL_SOURCES = [
     "dslash_staggered.hip",
     "laplace.hip",
     "contract.hip",
+    "multi_blas.hip",
     "dslash_dwf.hip",
     "dslash_dwf_fused.hip",
     "dslash_wilson_mrhs.hip",

@@ -472,6 +472,116 @@ static at::Tensor evec_project(std::vector<at::Tensor> evecs,
   return out;
 }
 
+// multi-BLAS family (csrc/multi_blas.h): vector sets as lists of field
+// tensors, read in place. Every tensor of a call has one dtype and one
+// numel; half fields are [..., n_chunk, V, w] with a norm per site.
+static std::vector<BlasField> multi_blas_fields(
+    const char *what, const std::vector<at::Tensor> &fs,
+    const std::vector<at::Tensor> &norms, const at::Tensor &like) {
+  TORCH_CHECK(!fs.empty() && (int64_t)fs.size() <= QA_MB_MAXV, what,
+              ": 1 to ", QA_MB_MAXV, " vectors per side of a launch");
+  const bool half = like.scalar_type() == at::kHalf;
+  TORCH_CHECK(!half || norms.size() == fs.size(), what,
+              ": half fields carry a norm per site");
+  std::vector<BlasField> out;
+  for (size_t i = 0; i < fs.size(); ++i) {
+    const at::Tensor &f = fs[i];
+    TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
+                    f.scalar_type() == like.scalar_type() &&
+                    f.numel() == like.numel() &&
+                    (uintptr_t)f.data_ptr() % 16 == 0,
+                what, ": contiguous 16-byte aligned GPU fields of one "
+                      "precision and size");
+    void *norm = nullptr;
+    if (half) {
+      const at::Tensor &n = norms[i];
+      TORCH_CHECK(n.is_cuda() && n.is_contiguous() &&
+                      n.scalar_type() == at::kFloat && f.dim() >= 3 &&
+                      n.numel() * f.size(-3) * f.size(-1) == f.numel(),
+                  what, ": half norm does not match its field");
+      norm = n.data_ptr();
+    }
+    out.push_back(BlasField{f.data_ptr(), norm, 0});
+  }
+  return out;
+}
+
+// partial [blocks][N][M] complex128 of G[i,j] = <x_i, y_j>; the caller adds
+// the blocks. same: ys is xs, read once, G exactly Hermitian
+static at::Tensor multi_cdot(std::vector<at::Tensor> xs,
+                             std::vector<at::Tensor> x_norms,
+                             std::vector<at::Tensor> ys,
+                             std::vector<at::Tensor> y_norms, bool same) {
+  TORCH_CHECK(!xs.empty(), "multi_cdot: no vectors");
+  const at::Tensor &like = xs[0];
+  MultiBlasCall c{};
+  c.prec = prec_of(like);
+  TORCH_CHECK(c.prec <= 2 && like.numel() >= 2 && like.numel() % 2 == 0,
+              "multi_cdot: double, single or half complex fields");
+  auto x = multi_blas_fields("multi_cdot", xs, x_norms, like);
+  auto y = multi_blas_fields("multi_cdot", ys, y_norms, like);
+  TORCH_CHECK(!same || xs.size() == ys.size(), "multi_cdot: same needs N == M");
+  c.x = x.data();
+  c.nx = (int)x.size();
+  c.y = y.data();
+  c.ny = (int)y.size();
+  c.len = like.numel() / 2;
+  c.same = same;
+  if (c.prec == 2) {
+    c.half_cw = (int)like.size(-1) / 2;
+    c.half_V = like.size(-2);
+    c.half_nchV = like.size(-3) * like.size(-2);
+  }
+  auto out = at::empty({multi_cdot_blocks(c.len), c.nx, c.ny},
+                       like.options().dtype(at::kComplexDouble));
+  c.partial = out.data_ptr();
+  TORCH_CHECK(launch_multi_cdot(c, stream()),
+              "multi_cdot: no kernel for this call");
+  check_launch("multi_cdot");
+  return out;
+}
+
+// out_i = beta y_i + sum_j A[i,j] x_j; A: CPU complex [n_out][n_in] of the
+// fields' precision. beta = false never reads ys (pass an empty list)
+static void multi_caxpy(std::vector<at::Tensor> outs,
+                        std::vector<at::Tensor> ys,
+                        std::vector<at::Tensor> xs, at::Tensor A, bool beta) {
+  TORCH_CHECK(!xs.empty() && !outs.empty(), "multi_caxpy: no vectors");
+  const at::Tensor &like = xs[0];
+  MultiBlasCall c{};
+  c.prec = prec_of(like);
+  TORCH_CHECK(c.prec <= 1 && like.numel() >= 2 && like.numel() % 2 == 0,
+              "multi_caxpy: double or single complex fields");
+  auto x = multi_blas_fields("multi_caxpy", xs, {}, like);
+  auto o = multi_blas_fields("multi_caxpy", outs, {}, like);
+  std::vector<BlasField> y;
+  if (beta) {
+    y = multi_blas_fields("multi_caxpy", ys, {}, like);
+    TORCH_CHECK(y.size() == o.size(), "multi_caxpy: one y per output");
+  }
+  for (const auto &of : o)
+    for (const auto &xf : x)
+      TORCH_CHECK(of.data != xf.data, "multi_caxpy: an output is an input x");
+  TORCH_CHECK(A.is_cpu() && A.is_contiguous() && A.dim() == 2 &&
+                  A.size(0) == (int64_t)o.size() &&
+                  A.size(1) == (int64_t)x.size() &&
+                  A.scalar_type() ==
+                      (c.prec == 0 ? at::kComplexDouble : at::kComplexFloat),
+              "multi_caxpy: A is CPU complex [n_out][n_in] of the fields' "
+              "precision");
+  c.x = x.data();
+  c.nx = (int)x.size();
+  c.y = beta ? y.data() : o.data();
+  c.ny = (int)o.size();
+  c.out = o.data();
+  c.len = like.numel() / 2;
+  c.A = A.data_ptr();
+  c.beta = beta ? 1 : 0;
+  TORCH_CHECK(launch_multi_caxpy(c, stream()),
+              "multi_caxpy: no kernel for this call");
+  check_launch("multi_caxpy");
+}
+
 static at::Tensor blas_op(int64_t op, double a, double b, at::Tensor x,
                           at::Tensor x_n, at::Tensor y, at::Tensor y_n,
                           int64_t Vcb, int64_t sites, double c2 = 0.0,
@@ -1252,6 +1362,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-tile momentum-projected slice sums of the 16 gamma traces");
   m.def("evec_project", &evec_project,
         "per-tile slice sums of <evec_i | psi> per spin");
+  m.def("multi_cdot", &multi_cdot,
+        "per-block partials of the Gram matrix <x_i, y_j> of two vector sets");
+  m.def("multi_caxpy", &multi_caxpy,
+        "out_i = beta y_i + sum_j A[i,j] x_j over a vector set");
   m.def("set_dslash_block", &set_dslash_block, "autotuner: dslash workgroup size");
   m.def("set_dslash_waves", &set_dslash_waves,
         "occupancy experiment: 0 default, 3 = 64-thread/3-wave variant "

@@ -287,6 +287,32 @@ bool launch_contract_slices(const ContractCall &c, hipStream_t st);
 bool launch_evec_project(const EvecProjectCall &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// multi-BLAS family (csrc/multi_blas.h): vector-set dots and block caxpy on
+// flat runs of `len` complex numbers. Each launcher returns false, and
+// launches nothing, when the precision has no instantiation, the call is out
+// of range or the coefficient table could not be staged.
+#define QA_MB_MAXV 64  // vectors per side of one launch
+struct MultiBlasCall {
+  int prec;             // 0 double, 1 single, 2 half (dots only)
+  const BlasField *x;   // nx vectors (Vcb unused)
+  int nx;
+  const BlasField *y;   // cdot: ny right-hand vectors; caxpy: the beta operand
+  int ny;               // caxpy: number of outputs
+  const BlasField *out;  // caxpy: ny outputs, none of them one of x
+  long len;             // complex numbers per vector
+  bool same;            // cdot: y is x (ny == nx): staged once, G Hermitian
+  // half: complex numbers per chunk (1, 2 or 4), sites and chunks per parity
+  int half_cw;
+  long half_V, half_nchV;
+  void *partial;        // cdot: [multi_cdot_blocks(len)][nx][ny] complex double
+  const void *A;        // caxpy: host [ny][nx] complex of the storage type
+  int beta;             // caxpy: 0 (y never read) or 1
+};
+long multi_cdot_blocks(long len);
+bool launch_multi_cdot(const MultiBlasCall &c, hipStream_t st);
+bool launch_multi_caxpy(const MultiBlasCall &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // 5th-dimension family (csrc/dslash_dwf.h): Moebius, zMobius and EOFA share
 // one call base. Each launcher returns false, and launches nothing, when
 // the precision has no instantiation or a table could not be staged.

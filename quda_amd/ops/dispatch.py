@@ -1262,3 +1262,104 @@ def evec_project_slices(evecs, psi: SpinorField, reduct_dim: int,
     trace_record("evec_project",
                  f"{psi.precision}/rd{reduct_dim}/n{len(evecs)}")
     return torch.sum(part, dim=0)
+
+
+# ---------------------------------------------------------------------------
+# multi-BLAS family (csrc/multi_blas.h): vector-set dots, block caxpy and the
+# basis rotation under ops/multi_blas.py and the TRLM eigensolver. Opt-in:
+# QUDA_AMD_NATIVE_MULTI_BLAS=1 or native=True.
+# ---------------------------------------------------------------------------
+
+MULTI_BLAS_MAXV = 64  # QA_MB_MAXV, vectors per side of one launch
+
+
+def native_multi_blas_default() -> bool:
+    """QUDA_AMD_NATIVE_MULTI_BLAS=1 opts into the HIP multi-BLAS kernels
+    (default off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_MULTI_BLAS", "0") == "1"
+
+
+def multi_blas_eligible(fields, native=None, writes: bool = False) -> bool:
+    """True when the multi-BLAS kernels may serve the call: the flag is on
+    (native, or the environment when native is None), every field on the GPU,
+    contiguous and 16-byte aligned, of one precision and one data shape, the
+    precision double, single or (for reads only) half, and a single-rank
+    lattice. Everything else, an explicit native=True included, takes the
+    torch path unchanged."""
+    from ..parallel import comms
+    if not (native_multi_blas_default() if native is None else bool(native)):
+        return False
+    fields = list(fields)
+    if not fields or not all(f.device.type == "cuda" for f in fields):
+        return False
+    prec, shape = fields[0].precision, fields[0].data.shape
+    return bool(
+        prec in (("double", "single") if writes
+                 else ("double", "single", "half"))
+        and all(f.precision == prec and f.data.shape == shape
+                and f.data.is_contiguous() and f.data.data_ptr() % 16 == 0
+                for f in fields)
+        and comms.comm_mask() == 0)
+
+
+def _same_set(xs, ys) -> bool:
+    return xs is ys or (len(xs) == len(ys)
+                        and all(a is b for a, b in zip(xs, ys)))
+
+
+def multi_cdot(xs, ys) -> torch.Tensor:
+    """[N, M] complex128 G[i,j] = <x_i, y_j>, products and sums in double.
+    Sets beyond 64 vectors are split here; the per-workgroup partials of a
+    launch are added in block order, so two calls agree bitwise. When ys
+    holds the very fields of xs the set is read once and G is exactly
+    Hermitian. The caller has checked multi_blas_eligible."""
+    ext = hip_ext()
+    xs, ys = list(xs), list(ys)
+    same = _same_set(xs, ys)
+    N, M, B = len(xs), len(ys), MULTI_BLAS_MAXV
+    G = torch.empty((N, M), dtype=torch.complex128, device=xs[0].device)
+    for i0 in range(0, N, B):
+        xa = xs[i0:i0 + B]
+        for j0 in range(i0 if same else 0, M, B):
+            ya = ys[j0:j0 + B]
+            part = ext.multi_cdot(
+                [f.data for f in xa], [norm_or_empty(f) for f in xa],
+                [f.data for f in ya], [norm_or_empty(f) for f in ya],
+                same and i0 == j0)
+            blk = torch.sum(part, dim=0)
+            G[i0:i0 + B, j0:j0 + B] = blk
+            if same and i0 != j0:
+                G[j0:j0 + B, i0:i0 + B] = blk.conj().mT
+    trace_record("multi_cdot",
+                 f"{xs[0].precision}/{N}x{M}{'/same' if same else ''}")
+    return G
+
+
+def multi_caxpy(A: torch.Tensor, xs, ys, outs=None):
+    """out_i = y_i + sum_j A[i,j] x_j in the fields' precision (double or
+    single); outs None updates ys in place. ys None is the rotation
+    out_i = sum_j A[i,j] x_j, which never reads outs. A is [len(outs),
+    len(xs)] complex, rounded here to the compute type; more than 64 inputs
+    are split, the later slices accumulating onto the partial result. No
+    output may be one of xs. The caller has checked multi_blas_eligible."""
+    ext = hip_ext()
+    xs = list(xs)
+    outs = list(ys if outs is None else outs)
+    ctype = (torch.complex128 if xs[0].precision == "double"
+             else torch.complex64)
+    A = torch.as_tensor(A).to(device="cpu", dtype=ctype)
+    B = MULTI_BLAS_MAXV
+    for i0 in range(0, len(outs), B):
+        oa = [f.data for f in outs[i0:i0 + B]]
+        for j0 in range(0, len(xs), B):
+            beta = ys is not None or j0 > 0
+            ya = ([f.data for f in ys[i0:i0 + B]]
+                  if ys is not None and j0 == 0 else oa)
+            ext.multi_caxpy(oa, ya if beta else [],
+                            [f.data for f in xs[j0:j0 + B]],
+                            A[i0:i0 + B, j0:j0 + B].contiguous(), beta)
+    trace_record("multi_caxpy",
+                 f"{xs[0].precision}/{len(outs)}x{len(xs)}"
+                 f"/b{0 if ys is None else 1}")
+    return outs

@@ -14,7 +14,8 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 
 from ..fields.spinor import SpinorField
-from ..ops import blas
+from ..ops import blas, dispatch
+from ..ops.multi_blas import block_caxpy, block_cdot, block_rotate
 
 
 @dataclass
@@ -80,6 +81,8 @@ def trlm_solve(op, n_ev: int, n_kr: int, x0: SpinorField, *,
     V = [_new_like(x0) for _ in range(n_kr + 1)]
     tmp = _new_like(x0)
     r = _new_like(x0)
+    # the HIP multi-BLAS kernels, when QUDA_AMD_NATIVE_MULTI_BLAS opts in
+    block_ops = dispatch.multi_blas_eligible(V + [r], writes=True)
     if blas.norm2(x0) == 0.0:
         x0.gaussian_(seed=1234)
     blas.copy(V[0], x0)
@@ -106,9 +109,16 @@ def trlm_solve(op, n_ev: int, n_kr: int, x0: SpinorField, *,
             for i in range(num_keep):
                 blas.axpy(-beta[i], V[i], r)
         # full re-orthogonalization (ref blockOrthogonalize)
-        for i in range(j + 1):
-            c = blas.c_dot(V[i], r)
-            blas.caxpy(-c, V[i], r)
+        if block_ops:
+            # block classical Gram-Schmidt, twice: each pass reads the basis
+            # once for the dots and once for the update
+            for _ in range(2):
+                c = block_cdot(V[:j + 1], [r])
+                block_caxpy(-c.mT, V[:j + 1], [r])
+        else:
+            for i in range(j + 1):
+                c = blas.c_dot(V[i], r)
+                blas.caxpy(-c, V[i], r)
         b = sqrt(blas.norm2(r))
         beta[j] = b
         if b > 0:
@@ -178,6 +188,8 @@ def trlm_solve(op, n_ev: int, n_kr: int, x0: SpinorField, *,
 def _rotate(V, Z, m):
     """Vnew_i = sum_j V[j] Z[j,i] (host-coefficient basis rotation)."""
     k = Z.shape[1]
+    if dispatch.multi_blas_eligible(V[:m], writes=True):
+        return block_rotate(V[:m], Z[:m])
     out = []
     for i in range(k):
         v = _new_like(V[0])
