@@ -39,6 +39,7 @@ KERNEL_SOURCES = [
     "coarse.hip",
     "heatbath.hip",
     "gauge_path.hip",
+    "gauge_fix.hip",
     "transfer.hip",
     "galerkin.hip",
 ]

@@ -1036,6 +1036,57 @@ static void check_path_lattice(const char *what, const at::Tensor &u,
   TORCH_CHECK(u.numel() == 4 * 2 * Vcb * 9, what, ": u is not [4,2,Vcb,3,3]");
 }
 
+static GaugeFixCall gauge_fix_call(const char *what, const at::Tensor &u,
+                                   const std::vector<int64_t> &dims,
+                                   int64_t parity_offset, int64_t Vcb,
+                                   int64_t dirs) {
+  check_path_lattice(what, u, dims, Vcb);
+  // even extents make Vcb a multiple of 8: the kernel's 8-site waves are
+  // never partly inside the lattice
+  TORCH_CHECK(Vcb % 8 == 0, what, ": Vcb must be a multiple of 8");
+  TORCH_CHECK(dirs == 3 || dirs == 4, what, ": dirs is 3 or 4");
+  GaugeFixCall c{};
+  c.u = u.data_ptr();
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  c.dirs = (int)dirs;
+  return c;
+}
+
+static void gauge_fix_ovr_half(at::Tensor u, std::vector<int64_t> dims,
+                               int64_t parity_offset, int64_t Vcb,
+                               int64_t parity, int64_t dirs, double omega,
+                               bool reunit) {
+  const char *what = "gauge_fix_ovr_half";
+  GaugeFixCall c = gauge_fix_call(what, u, dims, parity_offset, Vcb, dirs);
+  TORCH_CHECK(parity == 0 || parity == 1, what, ": parity is 0 or 1");
+  c.parity = (int)parity;
+  c.omega = omega;
+  c.reunit = reunit ? 1 : 0;
+  launch_gauge_fix_ovr(c, stream());
+  check_launch(what);
+}
+
+static at::Tensor gauge_fix_quality(at::Tensor u, std::vector<int64_t> dims,
+                                    int64_t parity_offset, int64_t Vcb,
+                                    int64_t dirs) {
+  const char *what = "gauge_fix_quality";
+  GaugeFixCall c = gauge_fix_call(what, u, dims, parity_offset, Vcb, dirs);
+  at::Tensor partials = at::empty({gauge_fix_quality_blocks(Vcb), 2},
+                                  u.options().dtype(at::kDouble));
+  launch_gauge_fix_quality(c, partials.data_ptr<double>(), stream());
+  check_launch(what);
+  return partials;
+}
+
+static void gauge_fix_reunit(at::Tensor u) {
+  TORCH_CHECK(u.is_cuda() && u.is_contiguous() &&
+                  u.scalar_type() == at::kComplexDouble &&
+                  u.numel() % 9 == 0,
+              "gauge_fix_reunit: u must be contiguous complex128 [...,3,3]");
+  launch_gauge_fix_reunit(u.data_ptr(), u.numel() / 9, stream());
+  check_launch("gauge_fix_reunit");
+}
+
 static void gauge_path_dir(at::Tensor out, at::Tensor u, at::Tensor steps,
                            at::Tensor lens, at::Tensor coefs,
                            std::vector<int64_t> dims, int64_t parity_offset,
@@ -1345,6 +1396,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "path-table force / path product of one direction (fused mom update)");
   m.def("gauge_loop_trace", &gauge_loop_trace,
         "per-site traces of a table of closed loops");
+  m.def("gauge_fix_ovr_half", &gauge_fix_ovr_half,
+        "overrelaxed gauge-fixing half-sweep of one parity, in place");
+  m.def("gauge_fix_quality", &gauge_fix_quality,
+        "per-block (sum |Delta|^2, sum Re tr U) partials [nblocks,2]");
+  m.def("gauge_fix_reunit", &gauge_fix_reunit,
+        "Gram-Schmidt re-orthonormalisation of every link, in place");
   m.def("flow_zmat_dir", &flow_zmat_dir, "wilson-flow Z = eps TA[S U^d]");
   m.def("flow_expmul_dir", &flow_expmul_dir, "U' = exp(Zc) U");
   m.def("stout_smear_dir", &stout_smear_dir,

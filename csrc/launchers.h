@@ -434,6 +434,24 @@ void launch_stout(const StoutCall &c, hipStream_t st);
 void launch_zmat(const StoutCall &c, hipStream_t st);    // Z = eps TA[S U^d]
 void launch_expmul(const StoutCall &c, hipStream_t st);  // U' = exp(Zc) U
 
+// overrelaxation gauge fixing (csrc/gauge_fix.hip), in place on the
+// [4][2][Vcb][3][3] complex double tensor; Vcb is a multiple of 8
+struct GaugeFixCall {
+  void *u;
+  LatDesc lat;
+  int parity;    // half-sweep: the active parity
+  int dirs;      // 4 Landau, 3 Coulomb
+  double omega;
+  int reunit;    // re-orthonormalise every link before its store
+};
+void launch_gauge_fix_ovr(const GaugeFixCall &c, hipStream_t st);
+void launch_gauge_fix_reunit(void *u, long nlinks, hipStream_t st);
+// quality: two doubles per block, (sum |Delta|^2, sum Re tr U) over both
+// parities; reads u, lat and dirs of the call
+long gauge_fix_quality_blocks(long Vcb);
+void launch_gauge_fix_quality(const GaugeFixCall &c, double *partials,
+                              hipStream_t st);
+
 // path-table force / path product and loop traces (csrc/gauge_path.hip).
 // A path is QA_PATH_STEPS int8 steps +-(nu+1), zero padded and 8-byte
 // aligned; tails hold at most 7 steps, closed loops 8.

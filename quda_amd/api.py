@@ -726,8 +726,11 @@ def gauss_mom_quda(seed: int) -> torch.Tensor:
 
 
 def compute_gauge_fixing_ovr_quda(gauge: str = "landau", **kw) -> None:
-    """Fix the resident field (ref: computeGaugeFixingOVRQuda)."""
+    """Fix the resident field (ref: computeGaugeFixingOVRQuda). Without a
+    `native` keyword QUDA_AMD_NATIVE_GAUGE_FIX decides (the C and Fortran
+    entries come through here)."""
     from .gauge.fix import gauge_fix_ovr
+    kw.setdefault("native", None)
     load_gauge_quda(gauge_fix_ovr(_R.u_complex, _R.geo, gauge=gauge, **kw),
                     _R.gauge_param)
 

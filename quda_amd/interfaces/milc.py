@@ -543,14 +543,15 @@ def qudaContractFT(x_milc: torch.Tensor, y_milc: torch.Tensor, momenta,
 # ---------------------------------------------------------------------------
 
 def qudaGaugeFixingOVR(gauge_dir: int = 4, *, max_iter: int = 200,
-                       omega: float = 1.7, tol: float = 1e-8):
+                       omega: float = 1.7, tol: float = 1e-8, native=None):
     """Overrelaxed gauge fixing of the resident field (gauge_dir 4 =
     Landau, 3 = Coulomb); refreshes the resident links like the
-    reference."""
+    reference. `omega` takes effect on the native path only (native=True,
+    or QUDA_AMD_NATIVE_GAUGE_FIX=1 when native is None)."""
     from ..gauge.fix import gauge_fix_ovr
     g = "landau" if gauge_dir == 4 else "coulomb"
     w = gauge_fix_ovr(api._R.u_complex, api._R.geo, gauge=g, omega=omega,
-                      max_iter=max_iter, tol=tol)
+                      max_iter=max_iter, tol=tol, native=native)
     api.load_gauge_quda(w, api._R.gauge_param)
     return w
 
