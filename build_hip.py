@@ -40,6 +40,7 @@ KERNEL_SOURCES = [
     "heatbath.hip",
     "gauge_path.hip",
     "gauge_fix.hip",
+    "clover_force.hip",
     "transfer.hip",
     "galerkin.hip",
 ]
@@ -87,9 +88,10 @@ def _headers_mtime() -> float:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(BUILD, exist_ok=True)
-    # regenerate projector header
-    subprocess.run([sys.executable, os.path.join(CSRC, "generate_proj.py")],
-                   check=True, capture_output=True)
+    # regenerate the projector and sigma headers
+    for gen in ("generate_proj.py", "generate_sigma.py"):
+        subprocess.run([sys.executable, os.path.join(CSRC, gen)],
+                       check=True, capture_output=True)
     tinc, tlink = torch_flags()
     hmt = _headers_mtime()
     jobs = []

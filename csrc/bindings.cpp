@@ -1131,6 +1131,79 @@ static void gauge_path_dir(at::Tensor out, at::Tensor u, at::Tensor steps,
   check_launch(what);
 }
 
+// checks shared by the two clover-force entries; u gives lattice and device
+static CloverForceCall clover_force_call(const char *what, const at::Tensor &u,
+                                         const at::Tensor &h,
+                                         const at::Tensor &x,
+                                         const at::Tensor &y,
+                                         const at::Tensor &coefs,
+                                         bool need_h,
+                                         const std::vector<int64_t> &dims,
+                                         int64_t parity_offset, int64_t Vcb) {
+  check_path_lattice(what, u, dims, Vcb);
+  // even extents make Vcb a multiple of 8: whole waves of 8-lane items
+  TORCH_CHECK(Vcb % 8 == 0, what, ": Vcb must be a multiple of 8");
+  auto cplx_on_dev = [&](const at::Tensor &t) {
+    return t.is_cuda() && t.is_contiguous() &&
+           t.scalar_type() == at::kComplexDouble && t.device() == u.device();
+  };
+  const int64_t n = coefs.numel();
+  TORCH_CHECK(n >= 1 && coefs.is_contiguous() &&
+                  coefs.scalar_type() == at::kDouble &&
+                  coefs.device() == u.device(),
+              what, ": coefs must be float64 [n], n >= 1, on u's device");
+  TORCH_CHECK(cplx_on_dev(x) && cplx_on_dev(y) &&
+                  x.numel() == n * 2 * Vcb * 12 && y.numel() == x.numel(),
+              what, ": x and y must be complex128 [n,2,Vcb,4,3] on u's device");
+  if (need_h)
+    TORCH_CHECK(cplx_on_dev(h) && h.numel() == 6 * 2 * Vcb * 9 &&
+                    h.data_ptr() != u.data_ptr(),
+                what, ": h must be complex128 [6,2,Vcb,3,3] on u's device");
+  CloverForceCall c{};
+  c.u = u.data_ptr();
+  c.h = need_h ? h.data_ptr() : nullptr;
+  c.x = x.data_ptr();
+  c.y = y.data_ptr();
+  c.coefs = coefs.data_ptr<double>();
+  c.n = (int)n;
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  return c;
+}
+
+static void clover_force_oprod(at::Tensor h, at::Tensor u, at::Tensor x,
+                               at::Tensor y, at::Tensor coefs,
+                               std::vector<int64_t> dims,
+                               int64_t parity_offset, int64_t Vcb) {
+  const char *what = "clover_force_oprod";
+  CloverForceCall c = clover_force_call(what, u, h, x, y, coefs, true, dims,
+                                        parity_offset, Vcb);
+  launch_clover_sigma_oprod(c, stream());
+  check_launch(what);
+}
+
+static void clover_force_dir(at::Tensor out, at::Tensor u, at::Tensor h,
+                             at::Tensor x, at::Tensor y, at::Tensor coefs,
+                             std::vector<int64_t> dims, int64_t parity_offset,
+                             int64_t Vcb, double kappa, double csw, double dt,
+                             bool accumulate) {
+  const char *what = "clover_force_dir";
+  CloverForceCall c = clover_force_call(what, u, h, x, y, coefs, csw != 0.0,
+                                        dims, parity_offset, Vcb);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+                  out.scalar_type() == at::kComplexDouble &&
+                  out.numel() == u.numel() && out.device() == u.device() &&
+                  out.data_ptr() != u.data_ptr() &&
+                  (csw == 0.0 || out.data_ptr() != h.data_ptr()),
+              what, ": out must be a separate tensor shaped like u");
+  c.out = out.data_ptr();
+  c.kappa = kappa;
+  c.csw = csw;
+  c.dt = dt;
+  c.accumulate = accumulate;
+  launch_clover_force(c, stream());
+  check_launch(what);
+}
+
 static void gauge_loop_trace(at::Tensor tr, at::Tensor u, at::Tensor steps,
                              at::Tensor lens, std::vector<int64_t> dims,
                              int64_t parity_offset, int64_t Vcb) {
@@ -1396,6 +1469,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "path-table force / path product of one direction (fused mom update)");
   m.def("gauge_loop_trace", &gauge_loop_trace,
         "per-site traces of a table of closed loops");
+  m.def("clover_force_oprod", &clover_force_oprod,
+        "clover force: the six sigma outer products H_munu per site");
+  m.def("clover_force_dir", &clover_force_dir,
+        "Wilson-clover fermion force, all directions (fused mom update)");
   m.def("gauge_fix_ovr_half", &gauge_fix_ovr_half,
         "overrelaxed gauge-fixing half-sweep of one parity, in place");
   m.def("gauge_fix_quality", &gauge_fix_quality,

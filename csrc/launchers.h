@@ -483,6 +483,26 @@ struct LoopTraceCall {
 };
 void launch_loop_trace(const LoopTraceCall &c, hipStream_t st);
 
+// Wilson-clover pseudofermion force (csrc/clover_force.hip): the sigma
+// outer product H and the force of all four directions; Vcb is a multiple
+// of 8.
+struct CloverForceCall {
+  void *out;            // force: [4][2][Vcb][3][3], F or the momentum
+  const void *u;        // force: gauge, never aliases out
+  void *h;              // [6][2][Vcb][3][3]; written by the outer product,
+                        // read by the force (unused when csw == 0)
+  const void *x;        // [n][2][Vcb][4][3] complex double
+  const void *y;
+  const double *coefs;  // [n]
+  int n;
+  LatDesc lat;
+  double kappa, csw;
+  double dt;            // accumulate: out += dt * F
+  bool accumulate;      // read-modify-write out (fused momentum update)
+};
+void launch_clover_sigma_oprod(const CloverForceCall &c, hipStream_t st);
+void launch_clover_force(const CloverForceCall &c, hipStream_t st);
+
 // ---------------------------------------------------------------------------
 // multigrid transfer, fine Wilson level (csrc/transfer.hip). Double/single.
 struct TransferCall {

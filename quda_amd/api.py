@@ -820,13 +820,14 @@ def blas_gemm_quda(a: torch.Tensor, b: torch.Tensor,
 
 
 def compute_clover_force_quda(kappa: float, csw: float, x_sol: torch.Tensor,
-                              seed: int = 0) -> torch.Tensor:
+                              seed: int = 0, native=None) -> torch.Tensor:
     """ref: computeCloverForceQuda — clover-fermion force on the resident
     gauge for pseudofermion phi (autograd-exact; see
-    gauge.fermion_force.clover_fermion_force)."""
+    gauge.fermion_force.clover_fermion_force, also for `native`)."""
     from .gauge.fermion_force import clover_fermion_force
     phi = _wrap(x_sol, InvertParam(kappa=kappa), 2)
-    S, F = clover_fermion_force(_R.u_complex, _R.geo, kappa, csw, phi)
+    S, F = clover_fermion_force(_R.u_complex, _R.geo, kappa, csw, phi,
+                                native=native)
     return F
 
 

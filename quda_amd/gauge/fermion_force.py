@@ -63,10 +63,12 @@ def pseudofermion_refresh(d: DiracWilson, seed: int) -> SpinorField:
 
 def fermion_action_and_force(u: torch.Tensor, geo: LatticeGeometry,
                              kappa: float, phi: SpinorField, *,
-                             cg_tol: float = 1e-10, cg_maxiter: int = 2000
-                             ) -> Tuple[float, torch.Tensor]:
+                             cg_tol: float = 1e-10, cg_maxiter: int = 2000,
+                             native=None) -> Tuple[float, torch.Tensor]:
     """S_f = phi^dag (M Mdag)^{-1} phi (global) and its MD force
-    (multi-rank: the analytic Wilson force uses distributed shifts)."""
+    (multi-rank: the analytic Wilson force uses distributed shifts).
+    `native`: the csw = 0 case of clover_force_from_solutions when
+    clover_force_eligible, the einsum force otherwise."""
     g = GaugeField(geo, "double", phi.device).from_complex(u)
     d = DiracWilson(g, kappa)
     X = d.new_spinor(n_parity=2)
@@ -76,7 +78,11 @@ def fermion_action_and_force(u: torch.Tensor, geo: LatticeGeometry,
     Y = d.new_spinor(n_parity=2)
     d.M(Y, X, dagger=True)
     S_f = blas.re_dot(phi, X)
-    F = wilson_fermion_force(u, geo, kappa, X.to_complex(), Y.to_complex())
+    Xc, Yc = X.to_complex(), Y.to_complex()
+    if clover_force_eligible(u, Xc[None], Yc[None], native):
+        return S_f, clover_force_from_solutions(u, geo, kappa, 0.0, Xc, Yc,
+                                                native=True)
+    F = wilson_fermion_force(u, geo, kappa, Xc, Yc)
     return S_f, F
 
 
@@ -152,23 +158,134 @@ def autograd_fermion_force(u: torch.Tensor, geo: LatticeGeometry,
     return F
 
 
-def clover_fermion_force(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
-                         csw: float, phi: SpinorField, *,
-                         cg_tol: float = 1e-10, cg_maxiter: int = 2000):
-    """S_f and force for the two-flavor Wilson-CLOVER action
-    (M = A(U) - kappa D with the clover term differentiated through its
-    field-strength construction)."""
-    from ..fields.clover import CloverField
-    from ..models import DiracClover
+# ---------------------------------------------------------------------------
+# native Wilson-clover force (csrc/clover_force.hip). Opt-in:
+# QUDA_AMD_NATIVE_CLOVER_FORCE=1 or native=True. Covers the unpreconditioned
+# two-flavour operator M = A(U) - kappa D only; Hasenbusch, RHMC and the
+# HISQ forces below stay on autograd.
+#
+# With dS = -2 Re sum_i c_i <X_i, dM Y_i> the hop part is the module
+# docstring's G1/G2 form. The clover part: A = 1 + kappa csw sum_{mu<nu}
+# sigma_munu (x) F_munu, F = (Q - Q^d)/(8i) traceless, so X^d (sigma (x) dF) Y
+# = tr[dF O] with O_ji = sum_st Y_tj sigma_st conj(X_si), and the trace
+# subtraction and Q - Q^d reduce Re tr[dF O] to (1/8) Im tr[dQ H], H = Ohat +
+# Ohat^d hermitian traceless. U_mu(x) sits in the upper and lower plaquette
+# of every nu != mu; each is a leaf of Q at its four corners, with the plane's
+# orientation for the upper and against it for the lower one (H_munu =
+# -H_numu). Hence
+#   F_mu(x) = kappa TA[U G1 - G2 U^d + (i csw/8) U C_mu(x)],
+#   C = sum_nu sum_{+-} +-(H1 A1A2A3 + A1 H2 A2A3 + A1A2 H3 A3 + A1A2A3 H0),
+# A1 A2 A3 the staple from x+mu back to x, H_k at the corner before A_k.
+# ---------------------------------------------------------------------------
+
+def native_clover_force_default() -> bool:
+    """QUDA_AMD_NATIVE_CLOVER_FORCE=1 opts into the HIP clover-force
+    kernels (default off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_CLOVER_FORCE", "0") == "1"
+
+
+def clover_force_eligible(u: torch.Tensor, X, Y, native=None) -> bool:
+    """True when the flag is on (native, or the environment when native is
+    None), u passes gauge_native_eligible and X, Y are complex128
+    [n,2,Vcb,4,3] tensors on u's device. Everything else takes the torch
+    path, an explicit native=True included."""
+    from .ops import gauge_native_eligible
+    flag = native_clover_force_default() if native is None else bool(native)
+    if not (flag and gauge_native_eligible(u, True) and u.dim() == 5):
+        return False
+    want = (2, u.shape[2], 4, 3)
+    return all(isinstance(t, torch.Tensor) and t.dtype == torch.complex128
+               and t.device == u.device and t.dim() == 5
+               and tuple(t.shape[1:]) == want for t in (X, Y)
+               ) and X.shape[0] == Y.shape[0] >= 1
+
+
+def _stack_pairs(X, Y, coeffs):
+    if isinstance(X, torch.Tensor) and X.dim() == 4:
+        X, Y = X[None], Y[None]
+    n = X.shape[0] if isinstance(X, torch.Tensor) and X.dim() == 5 else 0
+    c = [1.0] * n if coeffs is None else [float(v) for v in coeffs]
+    return X, Y, c
+
+
+def clover_sigma_oprod(geo: LatticeGeometry, X: torch.Tensor,
+                       Y: torch.Tensor, coeffs, u: torch.Tensor
+                       ) -> torch.Tensor:
+    """[6,2,Vcb,3,3] hermitian traceless H_munu(x) from k_clover_sigma_oprod
+    (planes (0,1),(0,2),(0,3),(1,2),(1,3),(2,3)); callers check
+    clover_force_eligible first."""
+    from ..ops.dispatch import hip_ext
+    h = torch.empty((6, 2, geo.volume_cb, 3, 3), dtype=u.dtype,
+                    device=u.device)
+    c = torch.tensor(coeffs, dtype=torch.float64, device=u.device)
+    hip_ext().clover_force_oprod(h, u.contiguous(), X.contiguous(),
+                                 Y.contiguous(), c, list(geo.dims),
+                                 geo.parity_offset, geo.volume_cb)
+    return h
+
+
+def clover_force_from_solutions(u: torch.Tensor, geo: LatticeGeometry,
+                                kappa: float, csw: float, X, Y, coeffs=None,
+                                *, mom: torch.Tensor = None, dt: float = None,
+                                native=None) -> torch.Tensor:
+    """MD force of sum_i c_i [-2 Re <X_i, dM Y_i>] for the unpreconditioned
+    M = A(U) - kappa D; X, Y are [2,Vcb,4,3] or stacked [n,2,Vcb,4,3].
+    Eligible calls (clover_force_eligible) run k_clover_sigma_oprod and
+    k_clover_force; the rest sums autograd_fermion_force over the pairs
+    (wilson_fermion_force for csw == 0). With mom and dt the updated
+    momentum mom + dt*F is returned, in place on the native path."""
+    assert (mom is None) == (dt is None), "give mom and dt together"
+    X, Y, c = _stack_pairs(X, Y, coeffs)
+    if clover_force_eligible(u, X, Y, native):
+        from ..ops.dispatch import hip_ext
+        assert len(c) == X.shape[0], "one coefficient per pair"
+        uc, Xc, Yc = u.contiguous(), X.contiguous(), Y.contiguous()
+        h = (clover_sigma_oprod(geo, Xc, Yc, c, uc) if csw != 0.0
+             else torch.empty(0, dtype=u.dtype, device=u.device))
+        if mom is None:
+            out = torch.empty_like(uc)
+        else:
+            assert (mom.is_contiguous() and mom.shape == u.shape
+                    and mom.dtype == u.dtype and mom.device == u.device), \
+                "fused update needs a contiguous tensor shaped like u"
+            out = mom
+        hip_ext().clover_force_dir(
+            out, uc, h, Xc, Yc,
+            torch.tensor(c, dtype=torch.float64, device=u.device),
+            list(geo.dims), geo.parity_offset, geo.volume_cb, float(kappa),
+            float(csw), 0.0 if dt is None else float(dt), mom is not None)
+        return out
+    F = None
+    for ci, Xi, Yi in zip(c, X, Y):
+        if csw == 0.0:
+            Fi = wilson_fermion_force(u, geo, kappa, Xi, Yi)
+        else:
+            Fi = autograd_fermion_force(
+                u, geo, _clover_apply_M(geo, kappa, csw), Xi, Yi)
+        F = ci * Fi if F is None else F + ci * Fi
+    return F if mom is None else mom + dt * F
+
+
+def _clover_apply_M(geo: LatticeGeometry, kappa: float, csw: float):
+    """The torch-differentiable M = A(U) - kappa D of the clover force."""
     from ..ops.reference import clover_matrix, apply_clover, dslash_wilson_full
 
     def apply_M(u_t, psi):
         A = clover_matrix(u_t, geo, kappa, csw)
         return (apply_clover(A, psi)
                 - kappa * dslash_wilson_full(u_t, psi, geo))
+    return apply_M
 
-    # solve X = (M Mdag)^-1 phi with the fast path (kernels), grad with the
-    # oracle path
+
+def clover_solutions(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
+                     csw: float, phi: SpinorField, *, cg_tol: float = 1e-10,
+                     cg_maxiter: int = 2000):
+    """(S_f, X, Y) of the two-flavor Wilson-clover action: X = (M Mdag)^-1
+    phi by CG on the kernels, Y = Mdag X, both as [2,Vcb,4,3] tensors."""
+    from ..fields.clover import CloverField
+    from ..models import DiracClover
+    from ..ops.reference import clover_matrix
     g = GaugeField(geo, "double", phi.device).from_complex(u)
     A = clover_matrix(u, geo, kappa, csw)
     cl = CloverField(geo, "double", phi.device).from_matrices(A)
@@ -180,8 +297,27 @@ def clover_fermion_force(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
     Yf = d.new_spinor(n_parity=2)
     d.M(Yf, X, dagger=True)
     S_f = blas.re_dot(phi, X)
-    F = autograd_fermion_force(u, geo, apply_M, X.to_complex(),
-                               Yf.to_complex())
+    return S_f, X.to_complex(), Yf.to_complex()
+
+
+def clover_fermion_force(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
+                         csw: float, phi: SpinorField, *,
+                         cg_tol: float = 1e-10, cg_maxiter: int = 2000,
+                         native=None):
+    """S_f and force for the two-flavor Wilson-CLOVER action
+    (M = A(U) - kappa D with the clover term differentiated through its
+    field-strength construction). `native` (or
+    QUDA_AMD_NATIVE_CLOVER_FORCE=1 when None) takes the force from the HIP
+    kernels when clover_force_eligible; the solve is the same either way."""
+    # solve X = (M Mdag)^-1 phi with the fast path (kernels), grad with the
+    # oracle path
+    S_f, Xc, Yc = clover_solutions(u, geo, kappa, csw, phi, cg_tol=cg_tol,
+                                   cg_maxiter=cg_maxiter)
+    if clover_force_eligible(u, Xc[None], Yc[None], native):
+        return S_f, clover_force_from_solutions(u, geo, kappa, csw, Xc, Yc,
+                                                native=True)
+    F = autograd_fermion_force(u, geo, _clover_apply_M(geo, kappa, csw), Xc,
+                               Yc)
     return S_f, F
 
 

@@ -637,10 +637,11 @@ def qudaAsqtadForce(mass: float, source_milc: torch.Tensor,
 
 
 def qudaCloverForce(kappa: float, csw: float, source_milc: torch.Tensor,
-                    **kw):
+                    native=None, **kw):
     """Two-flavor Wilson-clover MD force (ref qudaCloverForce ->
     computeCloverForceQuda; clover-term derivative through the
-    differentiated field-strength construction)."""
+    differentiated field-strength construction). native: see
+    gauge.fermion_force.clover_fermion_force."""
     from ..fields.geometry import checkerboard_split
     from ..fields.spinor import SpinorField
     from ..gauge.fermion_force import clover_fermion_force
@@ -649,7 +650,7 @@ def qudaCloverForce(kappa: float, csw: float, source_milc: torch.Tensor,
     phi = SpinorField(geo, "double", str(b.device),
                       n_parity=2).from_complex(b)
     S, F = clover_fermion_force(api._R.u_complex, geo, kappa, csw, phi,
-                                **kw)
+                                native=native, **kw)
     return S, F
 
 
