@@ -41,6 +41,7 @@ KERNEL_SOURCES = [
     "gauge_path.hip",
     "gauge_fix.hip",
     "clover_force.hip",
+    "clover_term.hip",
     "transfer.hip",
     "galerkin.hip",
 ]

@@ -1204,6 +1204,60 @@ static void clover_force_dir(at::Tensor out, at::Tensor u, at::Tensor h,
   check_launch(what);
 }
 
+// data and inv empty: F_munu only (needs fmunu). Returns the per-block
+// partials [2][blocks][2], or an empty tensor in the F-only case.
+static at::Tensor clover_term(at::Tensor data, at::Tensor inv,
+                              at::Tensor fmunu, at::Tensor u,
+                              std::vector<int64_t> dims,
+                              int64_t parity_offset, int64_t Vcb,
+                              double coef) {
+  const char *what = "clover_term";
+  check_path_lattice(what, u, dims, Vcb);
+  TORCH_CHECK(Vcb % 8 == 0, what, ": Vcb must be a multiple of 8");
+  const bool factor = data.numel() != 0 || inv.numel() != 0;
+  const bool want_f = fmunu.numel() != 0;
+  TORCH_CHECK(factor || want_f, what, ": nothing to compute");
+  if (want_f)
+    TORCH_CHECK(fmunu.is_cuda() && fmunu.is_contiguous() &&
+                    fmunu.scalar_type() == at::kComplexDouble &&
+                    fmunu.numel() == 6 * 2 * Vcb * 9 &&
+                    fmunu.device() == u.device() &&
+                    fmunu.data_ptr() != u.data_ptr(),
+                what, ": fmunu must be complex128 [6,2,Vcb,3,3] on u's device");
+  CloverTermCall c{};
+  c.u = u.data_ptr();
+  c.fmunu = want_f ? fmunu.data_ptr() : nullptr;
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  c.coef = coef;
+  c.factor = factor;
+  at::Tensor partials = at::empty(
+      {factor ? 2 : 0, clover_term_blocks(Vcb), 2},
+      u.options().dtype(at::kDouble));
+  if (factor) {
+    const bool dbl = data.scalar_type() == at::kDouble;
+    TORCH_CHECK(dbl || data.scalar_type() == at::kFloat, what,
+                ": data must be float64 or float32");
+    const int64_t w = dbl ? 2 : 4;
+    for (const at::Tensor *t : {&data, &inv})
+      TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                      t->scalar_type() == data.scalar_type() &&
+                      t->device() == u.device() && t->dim() == 4 &&
+                      t->size(0) == 2 && t->size(1) == 72 / w &&
+                      t->size(2) == Vcb && t->size(3) == w &&
+                      (uintptr_t)t->data_ptr() % 16 == 0,
+                  what, ": data and inv must be [2,72/w,Vcb,w] on u's device");
+    TORCH_CHECK(data.data_ptr() != inv.data_ptr(), what,
+                ": data and inv must not alias");
+    c.data = data.data_ptr();
+    c.inv = inv.data_ptr();
+    c.partials = partials.data_ptr<double>();
+    c.prec = dbl ? 0 : 1;
+  }
+  launch_clover_term(c, stream());
+  check_launch(what);
+  return partials;
+}
+
 static void gauge_loop_trace(at::Tensor tr, at::Tensor u, at::Tensor steps,
                              at::Tensor lens, std::vector<int64_t> dims,
                              int64_t parity_offset, int64_t Vcb) {
@@ -1473,6 +1527,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "clover force: the six sigma outer products H_munu per site");
   m.def("clover_force_dir", &clover_force_dir,
         "Wilson-clover fermion force, all directions (fused mom update)");
+  m.def("clover_term", &clover_term,
+        "packed clover A, A^-1, tr log A partials and F_munu from the gauge");
   m.def("gauge_fix_ovr_half", &gauge_fix_ovr_half,
         "overrelaxed gauge-fixing half-sweep of one parity, in place");
   m.def("gauge_fix_quality", &gauge_fix_quality,

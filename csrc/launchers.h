@@ -503,6 +503,23 @@ struct CloverForceCall {
 void launch_clover_sigma_oprod(const CloverForceCall &c, hipStream_t st);
 void launch_clover_force(const CloverForceCall &c, hipStream_t st);
 
+// clover-term construction (csrc/clover_term.hip): packed A and A^-1 in the
+// chunked CloverField layout, tr log A / bad-pivot partials and optionally
+// F_munu, one launch; Vcb is a multiple of 8.
+struct CloverTermCall {
+  void *data;        // [2][72/w][Vcb][w], w = 2 (double) or 4 (single)
+  void *inv;         // same shape: A^-1
+  double *partials;  // [2][blocks][2]: (sum log|d|, pivots <= 0) per block
+  void *fmunu;       // [6][2][Vcb][3][3] complex double, or null
+  const void *u;     // [4][2][Vcb][3][3] complex double
+  LatDesc lat;
+  double coef;       // kappa * csw
+  int prec;          // 0 double, 1 single (store type; arithmetic is double)
+  bool factor;       // false: F_munu only, data/inv/partials untouched
+};
+long clover_term_blocks(long Vcb);
+void launch_clover_term(const CloverTermCall &c, hipStream_t st);
+
 // ---------------------------------------------------------------------------
 // multigrid transfer, fine Wilson level (csrc/transfer.hip). Double/single.
 struct TransferCall {

@@ -250,17 +250,37 @@ def load_gauge_quda(u: torch.Tensor, param: GaugeParam) -> None:
 
 
 def load_clover_quda(inv_param: InvertParam,
-                     clover: Optional[torch.Tensor] = None) -> None:
+                     clover: Optional[torch.Tensor] = None,
+                     native=None) -> None:
     """Build (or accept) the clover term for the resident gauge
     (ref: loadCloverQuda — with clover=None computes it from the resident
-    field like QUDA's compute_clover path)."""
+    field like QUDA's compute_clover path). `native` (or
+    QUDA_AMD_NATIVE_CLOVER=1 when None) builds it with the HIP kernel of
+    csrc/clover_term.hip where clover_term_eligible; _R.clover.trlog holds
+    (even, odd) tr log A whenever the term is computed here."""
     assert _R.geo is not None, "load_gauge_quda first"
+    from .fields.clover import _block_logdet, clover_term_eligible
+    dev, sp = _R.gauge.device, _R.gauge_sloppy.precision
+    kappa, csw = inv_param.kappa, inv_param.clover_csw
+    _R.clover = CloverField(_R.geo, _R.gauge.precision, dev)
+    cls = CloverField(_R.geo, sp, dev)
+    if clover is None and clover_term_eligible(_R.u_complex, _R.clover,
+                                               native):
+        _R.clover.from_gauge(_R.u_complex, kappa, csw, native=native)
+        if sp in ("double", "single"):
+            cls.from_gauge(_R.u_complex, kappa, csw, native=native)
+        else:
+            for inverse in (False, True):
+                p = pack_clover(_R.clover.to_complex(inverse=inverse))
+                (cls.inv_data if inverse else cls.data).copy_(
+                    cls._to_native(p))
+        _R.clover_sloppy = cls
+        return
     A = clover if clover is not None else ref.clover_matrix(
-        _R.u_complex, _R.geo, inv_param.kappa, inv_param.clover_csw)
-    _R.clover = CloverField(_R.geo, _R.gauge.precision,
-                            _R.gauge.device).from_matrices(A)
-    sp = _R.gauge_sloppy.precision
-    cls = CloverField(_R.geo, sp, _R.gauge.device)
+        _R.u_complex, _R.geo, kappa, csw)
+    _R.clover.from_matrices(A)
+    if clover is None:
+        _R.clover.trlog = _block_logdet(A)
     cls.data.copy_(cls._to_native(pack_clover(A)))
     inv = _R.clover.to_complex(inverse=True).to(_R.gauge.device)
     cls.inv_data.copy_(cls._to_native(pack_clover(inv)))

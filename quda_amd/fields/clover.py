@@ -60,6 +60,33 @@ def unpack_clover(p: torch.Tensor, dtype=torch.complex128) -> torch.Tensor:
     return A
 
 
+def native_clover_default() -> bool:
+    """QUDA_AMD_NATIVE_CLOVER=1 opts into the HIP clover-term kernel
+    (csrc/clover_term.hip; default off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_CLOVER", "0") == "1"
+
+
+def clover_term_eligible(u: torch.Tensor, field: "CloverField",
+                         native=None) -> bool:
+    """True when the flag is on (native, or the environment when native is
+    None), u is a [4,2,Vcb,3,3] tensor that passes gauge_native_eligible and
+    the field is double or single on u's device. Everything else takes the
+    torch path, an explicit native=True included."""
+    from ..gauge.ops import gauge_native_eligible
+    flag = native_clover_default() if native is None else bool(native)
+    return bool(flag and gauge_native_eligible(u, True) and u.dim() == 5
+                and field.precision in ("double", "single")
+                and field.device == u.device)
+
+
+def _block_logdet(A: torch.Tensor):
+    """(even, odd) tr log A of [2, V, 12, 12] from its chirality blocks."""
+    ld = sum(torch.linalg.slogdet(A[..., 6 * b:6 * b + 6, 6 * b:6 * b + 6])[1]
+             for b in range(2))
+    return tuple(ld.sum(-1).tolist())
+
+
 class CloverField:
     def __init__(self, geo: LatticeGeometry, precision: str = "double",
                  device="cpu"):
@@ -71,6 +98,7 @@ class CloverField:
         dt = DTYPE_OF[precision]
         self.data = torch.zeros(shape, dtype=dt, device=device)
         self.inv_data = torch.zeros(shape, dtype=dt, device=device)
+        self.trlog = None  # (even, odd) tr log A, set by from_gauge
 
     @property
     def device(self):
@@ -97,6 +125,29 @@ class CloverField:
             blk = A[..., 6 * b:6 * b + 6, 6 * b:6 * b + 6]
             Ainv[..., 6 * b:6 * b + 6, 6 * b:6 * b + 6] = torch.linalg.inv(blk)
         self.inv_data.copy_(self._to_native(pack_clover(Ainv)))
+        return self
+
+    def from_gauge(self, u: torch.Tensor, kappa: float, csw: float, *,
+                   native=None, fmunu: Optional[torch.Tensor] = None
+                   ) -> "CloverField":
+        """Build A = 1 + kappa csw sum sigma_munu (x) F_munu and A^-1 from
+        the gauge tensor u and set trlog = (even, odd) tr log A. Eligible
+        calls (clover_term_eligible) run k_clover_term, which also fills
+        fmunu ([6,2,Vcb,3,3]) when given; an indefinite A (a non-positive
+        pivot) and every other call run clover_matrix + from_matrices."""
+        from ..ops import dispatch, reference as ref
+        if clover_term_eligible(u, self, native):
+            te, to, bad = dispatch.clover_term(u, self.geo, kappa, csw, self,
+                                               fmunu)
+            if bad == 0:
+                self.trlog = (te, to)
+                return self
+        A = ref.clover_matrix(u, self.geo, kappa, csw)
+        if fmunu is not None:
+            F = ref.field_strength(u, self.geo)
+            fmunu.copy_(torch.stack([F[k] for k in sorted(F)]))
+        self.from_matrices(A)
+        self.trlog = _block_logdet(A)
         return self
 
     def to_complex(self, inverse: bool = False, dtype=torch.complex128):

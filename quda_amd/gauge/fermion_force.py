@@ -280,15 +280,17 @@ def _clover_apply_M(geo: LatticeGeometry, kappa: float, csw: float):
 
 def clover_solutions(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
                      csw: float, phi: SpinorField, *, cg_tol: float = 1e-10,
-                     cg_maxiter: int = 2000):
+                     cg_maxiter: int = 2000, native=False):
     """(S_f, X, Y) of the two-flavor Wilson-clover action: X = (M Mdag)^-1
-    phi by CG on the kernels, Y = Mdag X, both as [2,Vcb,4,3] tensors."""
+    phi by CG on the kernels, Y = Mdag X, both as [2,Vcb,4,3] tensors.
+    `native` goes to CloverField.from_gauge: True, or None with
+    QUDA_AMD_NATIVE_CLOVER=1, builds A and A^-1 with k_clover_term where
+    clover_term_eligible."""
     from ..fields.clover import CloverField
     from ..models import DiracClover
-    from ..ops.reference import clover_matrix
     g = GaugeField(geo, "double", phi.device).from_complex(u)
-    A = clover_matrix(u, geo, kappa, csw)
-    cl = CloverField(geo, "double", phi.device).from_matrices(A)
+    cl = CloverField(geo, "double", phi.device).from_gauge(
+        u, kappa, csw, native=native)
     d = DiracClover(g, cl, kappa)
     X = d.new_spinor(n_parity=2)
     st = cg_solve(_NormalOp(d, mmdag=True), X, phi, tol=cg_tol,
@@ -308,11 +310,17 @@ def clover_fermion_force(u: torch.Tensor, geo: LatticeGeometry, kappa: float,
     (M = A(U) - kappa D with the clover term differentiated through its
     field-strength construction). `native` (or
     QUDA_AMD_NATIVE_CLOVER_FORCE=1 when None) takes the force from the HIP
-    kernels when clover_force_eligible; the solve is the same either way."""
+    kernels when clover_force_eligible. With the native force on and
+    QUDA_AMD_NATIVE_CLOVER=1 the clover term of the solve comes from
+    k_clover_term as well, and clover_matrix is not called; without that
+    switch the solve is the same either way."""
     # solve X = (M Mdag)^-1 phi with the fast path (kernels), grad with the
     # oracle path
+    force_native = (native_clover_force_default() if native is None
+                    else bool(native))
     S_f, Xc, Yc = clover_solutions(u, geo, kappa, csw, phi, cg_tol=cg_tol,
-                                   cg_maxiter=cg_maxiter)
+                                   cg_maxiter=cg_maxiter,
+                                   native=None if force_native else False)
     if clover_force_eligible(u, Xc[None], Yc[None], native):
         return S_f, clover_force_from_solutions(u, geo, kappa, csw, Xc, Yc,
                                                 native=True)

@@ -1363,3 +1363,23 @@ def multi_caxpy(A: torch.Tensor, xs, ys, outs=None):
                  f"{xs[0].precision}/{len(outs)}x{len(xs)}"
                  f"/b{0 if ys is None else 1}")
     return outs
+
+
+def clover_term(u: torch.Tensor, geo, kappa: float, csw: float, out,
+                fmunu: Optional[torch.Tensor] = None):
+    """k_clover_term (csrc/clover_term.hip): the packed clover term
+    A = 1 + kappa csw sum sigma_munu (x) F_munu and A^-1 written into the
+    CloverField `out` (double or single) in its chunked layout, and F_munu
+    into `fmunu` ([6,2,Vcb,3,3] complex128) when given. Returns
+    (trlog_even, trlog_odd, bad_pivots): tr log A per parity and the number
+    of non-positive pivots (A indefinite when > 0; A^-1 and the logs are
+    then meaningless). The caller has checked clover_term_eligible."""
+    ext = hip_ext()
+    f = empty_tensor(u.dtype, u.device) if fmunu is None else fmunu
+    part = ext.clover_term(out.data, out.inv_data, f, u.contiguous(),
+                           list(geo.dims), geo.parity_offset, geo.volume_cb,
+                           float(kappa) * float(csw))
+    sums = part.sum(dim=1).cpu()
+    trace_record("clover_term", out.precision)
+    return (sums[0, 0].item(), sums[1, 0].item(),
+            int(sums[0, 1].item() + sums[1, 1].item()))
