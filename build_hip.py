@@ -38,6 +38,7 @@ KERNEL_SOURCES = [
     "dslash_wilson_mrhs.hip",
     "coarse.hip",
     "heatbath.hip",
+    "smear.hip",
     "gauge_path.hip",
     "gauge_fix.hip",
     "clover_force.hip",

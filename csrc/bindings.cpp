@@ -1036,6 +1036,65 @@ static void check_path_lattice(const char *what, const at::Tensor &u,
   TORCH_CHECK(u.numel() == 4 * 2 * Vcb * 9, what, ": u is not [4,2,Vcb,3,3]");
 }
 
+// one APE / HYP level; a table row is [mu, ns, (eta, a, b) x ns]
+static void smear_level(at::Tensor out, at::Tensor src, at::Tensor cen,
+                        std::vector<int64_t> dims, int64_t parity_offset,
+                        int64_t Vcb, std::vector<std::vector<int64_t>> table,
+                        double c0, double c1, int64_t proj) {
+  const char *what = "smear_level";
+  check_path_lattice(what, cen, dims, Vcb);
+  const int64_t No = (int64_t)table.size(), slot = 2 * Vcb * 9;
+  TORCH_CHECK(No >= 1 && No <= QA_SMEAR_MAX_OUT, what,
+              ": 1 to 12 outputs");
+  for (const at::Tensor *f : {&out, &src})
+    TORCH_CHECK(f->is_cuda() && f->is_contiguous() &&
+                    f->scalar_type() == at::kComplexDouble &&
+                    f->device() == cen.device() && f->numel() % slot == 0,
+                what, ": out and src must be contiguous complex128 "
+                      "[slots,2,Vcb,3,3] on cen's device");
+  const int64_t Ns = src.numel() / slot;
+  TORCH_CHECK(out.numel() == No * slot, what, ": out is not [No,2,Vcb,3,3]");
+  TORCH_CHECK(Ns >= 1 && Ns <= 16, what, ": src holds 1 to 16 slots");
+  TORCH_CHECK(out.data_ptr() != src.data_ptr() &&
+                  out.data_ptr() != cen.data_ptr(),
+              what, ": out must not alias src or cen");
+  TORCH_CHECK(proj == QA_SMEAR_PROJ_GS || proj == QA_SMEAR_PROJ_POLAR, what,
+              ": proj is 0 (Gram-Schmidt) or 1 (polar)");
+  SmearLevelCall c{};
+  for (int64_t o = 0; o < No; ++o) {
+    const auto &row = table[o];
+    TORCH_CHECK(row.size() >= 2 && row[1] >= 0 &&
+                    row[1] <= QA_SMEAR_MAX_STAPLES &&
+                    (int64_t)row.size() == 2 + 3 * row[1],
+                what, ": a row is [mu, ns <= 3, (eta, a, b) x ns]");
+    TORCH_CHECK(row[0] >= 0 && row[0] < 4, what, ": mu out of range");
+    c.mu[o] = (int)row[0];
+    c.ns[o] = (int)row[1];
+    for (int64_t k = 0; k < row[1]; ++k) {
+      const int64_t eta = row[2 + 3 * k], a = row[3 + 3 * k],
+                    b = row[4 + 3 * k];
+      TORCH_CHECK(eta >= 0 && eta < 4 && eta != row[0], what,
+                  ": eta must be a direction other than mu");
+      TORCH_CHECK(a >= 0 && a < Ns && b >= 0 && b < Ns, what,
+                  ": slot index outside src");
+      c.eta[o][k] = (int)eta;
+      c.a[o][k] = (int)a;
+      c.b[o][k] = (int)b;
+    }
+  }
+  c.out = out.data_ptr();
+  c.src = src.data_ptr();
+  c.cen = cen.data_ptr();
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  c.No = (int)No;
+  c.Ns = (int)Ns;
+  c.c0 = c0;
+  c.c1 = c1;
+  c.proj = (int)proj;
+  launch_smear_level(c, stream());
+  check_launch(what);
+}
+
 static GaugeFixCall gauge_fix_call(const char *what, const at::Tensor &u,
                                    const std::vector<int64_t> &dims,
                                    int64_t parity_offset, int64_t Vcb,
@@ -1535,6 +1594,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-block (sum |Delta|^2, sum Re tr U) partials [nblocks,2]");
   m.def("gauge_fix_reunit", &gauge_fix_reunit,
         "Gram-Schmidt re-orthonormalisation of every link, in place");
+  m.def("smear_level", &smear_level,
+        "one APE / HYP level: projected centre link plus table staples");
   m.def("flow_zmat_dir", &flow_zmat_dir, "wilson-flow Z = eps TA[S U^d]");
   m.def("flow_expmul_dir", &flow_expmul_dir, "U' = exp(Zc) U");
   m.def("stout_smear_dir", &stout_smear_dir,

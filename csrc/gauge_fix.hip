@@ -25,7 +25,7 @@
 #include "common.h"
 #include "launch_setup.h"
 #include "reduce.h"
-#include "su3_double.h"
+#include "su3_project.h"
 
 namespace {
 
@@ -76,36 +76,6 @@ __device__ __forceinline__ void ovr_hit(M3 &U, double weight, double omega) {
   }
 }
 
-// Gram-Schmidt on rows 0 and 1, row 2 = conj(row0 x row1)
-// (fields/gauge.py project_su3)
-__device__ __forceinline__ void reunit_su3(M3 &U) {
-  double n = 0.0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) n += U[0][c].re * U[0][c].re + U[0][c].im * U[0][c].im;
-  n = sqrt(n);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) U[0][c] = {U[0][c].re / n, U[0][c].im / n};
-  cd d = cjmul(U[0][0], U[1][0]);
-  d = cadd(d, cjmul(U[0][1], U[1][1]));
-  d = cadd(d, cjmul(U[0][2], U[1][2]));
-  n = 0.0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    cd t = cmul(d, U[0][c]);
-    U[1][c] = {U[1][c].re - t.re, U[1][c].im - t.im};
-    n += U[1][c].re * U[1][c].re + U[1][c].im * U[1][c].im;
-  }
-  n = sqrt(n);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) U[1][c] = {U[1][c].re / n, U[1][c].im / n};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int a = (c + 1) % 3, b = (c + 2) % 3;
-    cd x = cmul(U[0][a], U[1][b]), y = cmul(U[0][b], U[1][a]);
-    U[2][c] = {x.re - y.re, -(x.im - y.im)};
-  }
-}
-
 }  // namespace
 
 // Vcb is a multiple of 8 (all four extents are even; checked on the host),
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_gauge_fix_ovr(
   ovr_hit<0, 2>(U, weight, omega);
   ovr_hit<1, 2>(U, weight, omega);
   mat_dagger_if(U, bwd);
-  if (reunit) reunit_su3(U);
+  if (reunit) project_gs(U);
   store_link(g, d.Vcb, mu, p, j, U);
 }
 
@@ -145,7 +115,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_gauge_fix_reunit(
   if (t >= nlinks) return;
   M3 U;
   load_link(U, g, nlinks, 0, 0, t);
-  reunit_su3(U);
+  project_gs(U);
   store_link(g, nlinks, 0, 0, t, U);
 }
 

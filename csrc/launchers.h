@@ -434,6 +434,30 @@ void launch_stout(const StoutCall &c, hipStream_t st);
 void launch_zmat(const StoutCall &c, hipStream_t st);    // Z = eps TA[S U^d]
 void launch_expmul(const StoutCall &c, hipStream_t st);  // U' = exp(Zc) U
 
+// one level of APE / HYP link smearing (csrc/smear.hip):
+//   out[o] = Proj[c0 cen[mu_o] + c1 sum_{k<ns_o} staple(src[a_ok], src[b_ok];
+//                                                       mu_o, eta_ok)]
+// an output with ns = 0 copies cen[mu_o] through, unprojected
+#define QA_SMEAR_MAX_OUT 12
+#define QA_SMEAR_MAX_STAPLES 3
+#define QA_SMEAR_PROJ_GS 0
+#define QA_SMEAR_PROJ_POLAR 1
+struct SmearLevelCall {
+  void *out;        // [No][2][Vcb][3][3] complex double, aliases no input
+  const void *src;  // [Ns][2][Vcb][3][3]
+  const void *cen;  // [4][2][Vcb][3][3]
+  LatDesc lat;
+  int No, Ns;
+  int mu[QA_SMEAR_MAX_OUT];
+  int ns[QA_SMEAR_MAX_OUT];
+  int eta[QA_SMEAR_MAX_OUT][QA_SMEAR_MAX_STAPLES];
+  int a[QA_SMEAR_MAX_OUT][QA_SMEAR_MAX_STAPLES];  // slot of the mu_o links
+  int b[QA_SMEAR_MAX_OUT][QA_SMEAR_MAX_STAPLES];  // slot of the eta links
+  double c0, c1;
+  int proj;  // QA_SMEAR_PROJ_*
+};
+void launch_smear_level(const SmearLevelCall &c, hipStream_t st);
+
 // overrelaxation gauge fixing (csrc/gauge_fix.hip), in place on the
 // [4][2][Vcb][3][3] complex double tensor; Vcb is a multiple of 8
 struct GaugeFixCall {

@@ -604,11 +604,12 @@ def gauge_observables_quda() -> dict:
 
 
 def perform_gauge_smear_quda(kind: str, n_steps: int, coeff: float,
-                             measure: bool = False):
+                             measure: bool = False, native=None):
     """ref: performGaugeSmearQuda / performWFlowQuda — smears the resident
     field in place; measure=True (wilson_flow only) also returns the
     per-step (t, E_plaq, E_clover, t^2 E) history (the
-    gaugeSmearParam.meas_interval role)."""
+    gaugeSmearParam.meas_interval role). `native` overrides
+    QUDA_AMD_NATIVE_LINK_SMEAR for ape and hyp."""
     from .gauge import ape_smear, stout_smear, wilson_flow
     u = _R.u_complex
     if kind == "wilson_flow" and measure:
@@ -617,14 +618,14 @@ def perform_gauge_smear_quda(kind: str, n_steps: int, coeff: float,
         load_gauge_quda(u, _R.gauge_param)
         return hist
     if kind == "ape":
-        u = ape_smear(u, _R.geo, coeff, n_steps)
+        u = ape_smear(u, _R.geo, coeff, n_steps, native=native)
     elif kind == "stout":
         u = stout_smear(u, _R.geo, coeff, n_steps)
     elif kind == "wilson_flow":
         u = wilson_flow(u, _R.geo, coeff, n_steps)
     elif kind == "hyp":
         from .gauge import hyp_smear
-        u = hyp_smear(u, _R.geo, n_iter=n_steps)
+        u = hyp_smear(u, _R.geo, n_iter=n_steps, native=native)
     else:
         raise ValueError(kind)
     load_gauge_quda(u, _R.gauge_param)

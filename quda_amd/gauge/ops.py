@@ -126,10 +126,16 @@ def exp_su3(A: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
 
 
 def ape_smear(u: torch.Tensor, geo: LatticeGeometry, alpha: float,
-              n_iter: int = 1, spatial_only: bool = False) -> torch.Tensor:
+              n_iter: int = 1, spatial_only: bool = False,
+              native=None) -> torch.Tensor:
     """APE smearing: U' = Proj_SU3[(1-alpha) U + (alpha/6) staple]
-    (ref: lib/gauge_ape.cu)."""
+    (ref: lib/gauge_ape.cu). With the link-smearing flag on (native /
+    QUDA_AMD_NATIVE_LINK_SMEAR) and an eligible field the HIP level kernel
+    computes it, one launch per iteration."""
     from ..fields.gauge import project_su3
+    from .smear import ape_smear_native, link_smear_eligible
+    if link_smear_eligible(u, native):
+        return ape_smear_native(u, geo, alpha, n_iter, spatial_only)
     out = u
     dims = range(3) if spatial_only else range(4)
     for _ in range(n_iter):
@@ -549,16 +555,21 @@ def det_trace(u: torch.Tensor, geo: LatticeGeometry) -> tuple:
 
 
 def hyp_smear(u: torch.Tensor, geo: LatticeGeometry,
-              alpha: tuple = (0.75, 0.6, 0.3), n_iter: int = 1
-              ) -> torch.Tensor:
+              alpha: tuple = (0.75, 0.6, 0.3), n_iter: int = 1,
+              native=None) -> torch.Tensor:
     """HYP (hypercubic) smearing, Hasenfratz-Knechtli 3-level restricted
     staples (ref: lib/gauge_hyp.cu / kernels/gauge_hyp.cuh — re-derived:
     level-1 decorated links Vbar_{mu;nu rho} use staples only in the
     remaining direction, level-2 Vtil_{mu;nu} from Vbar staples, level 3
     assembles the fat link; each level applies the COVARIANT polar SU(3)
-    projection)."""
+    projection). With the link-smearing flag on (native /
+    QUDA_AMD_NATIVE_LINK_SMEAR) and an eligible field the HIP level kernel
+    computes it, three launches per iteration."""
     from ..fields.gauge import project_su3_polar as project_su3
     from ..parallel.halo import shift_lex
+    from .smear import hyp_smear_native, link_smear_eligible
+    if link_smear_eligible(u, native):
+        return hyp_smear_native(u, geo, alpha, n_iter)
     a1, a2, a3 = alpha
 
     def staple_dir(Ua, Ub, mu, nu):
@@ -618,15 +629,22 @@ def hyp_smear(u: torch.Tensor, geo: LatticeGeometry,
 
 def over_improved_stout_smear(u: torch.Tensor, geo: LatticeGeometry,
                               rho: float, n_iter: int = 1,
-                              epsilon: float = -0.25) -> torch.Tensor:
+                              epsilon: float = -0.25,
+                              native=None) -> torch.Tensor:
     """Over-improved stout smearing (Moran-Leinweber; ref: the
     over-improved branch of lib/gauge_stout.cu): the smearing direction
     is the traceless-antihermitian derivative of the action with
     plaquette weight (5 - 2 eps)/3 and rectangle weight -(1 - eps)/12;
     eps = 1 reduces EXACTLY to plain stout (rectangles drop out), the
     default eps = -0.25 is tuned to preserve instantons. Computed by
-    reverse-mode differentiation of the loop traces (single-rank)."""
+    reverse-mode differentiation of the loop traces (single-rank). With
+    the link-smearing flag on (native / QUDA_AMD_NATIVE_LINK_SMEAR) and an
+    eligible field the path-table HIP kernel forms the direction
+    analytically and k_expmul applies it."""
     from ..parallel import comms
+    from .smear import link_smear_eligible, over_improved_stout_native
+    if link_smear_eligible(u, native):
+        return over_improved_stout_native(u, geo, rho, n_iter, epsilon)
     assert comms.comm_size() == 1, "autograd smear direction: single-rank"
     c0 = (5.0 - 2.0 * epsilon) / 3.0
     c1 = -(1.0 - epsilon) / 12.0
