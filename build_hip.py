@@ -31,6 +31,7 @@ KERNEL_SOURCES = [
     "dslash_wilson_q.hip",
     "dslash_staggered.hip",
     "laplace.hip",
+    "kd.hip",
     "contract.hip",
     "multi_blas.hip",
     "dslash_dwf.hip",

@@ -1531,7 +1531,94 @@ static void galerkin_build(at::Tensor X, at::Tensor Y, at::Tensor scratch,
   check_launch(what);
 }
 
+// Kahler-Dirac block inverse (csrc/kd.hip). The table is one flat complex
+// tensor of 2304 entries per block: complex128 or complex64.
+static KdCall kd_call(const char *what, const at::Tensor &table,
+                      const std::vector<int64_t> &dims, int64_t parity_offset,
+                      int64_t Vcb, double mass) {
+  TORCH_CHECK(dims.size() == 4, what, ": dims must hold the 4 extents");
+  int64_t vol = 1;
+  for (int k = 0; k < 4; ++k) {
+    TORCH_CHECK(dims[k] >= 2 && dims[k] % 2 == 0, what,
+                ": extents must be even and >= 2");
+    vol *= dims[k];
+  }
+  TORCH_CHECK(Vcb > 0 && vol == 2 * Vcb && vol < (1LL << 31), what,
+              ": Vcb does not match dims");
+  TORCH_CHECK(mass > 0.0, what, ": the mass must be positive");
+  TORCH_CHECK(table.is_cuda() && table.is_contiguous() &&
+                  (table.scalar_type() == at::kComplexDouble ||
+                   table.scalar_type() == at::kComplexFloat) &&
+                  table.numel() == 2304 * (vol / 16),
+              what, ": table must be a contiguous complex GPU tensor of "
+                    "2304 entries per block");
+  KdCall c{};
+  c.lat = lat_of(dims, parity_offset, Vcb);
+  c.nblk = vol / 16;
+  c.table = table.data_ptr();
+  c.table_prec = table.scalar_type() == at::kComplexDouble ? 0 : 1;
+  c.mass = mass;
+  TORCH_CHECK(qa_kd_grid_ok(c), what, ": launch grid out of range");
+  return c;
+}
+
+static void kd_build(at::Tensor table, at::Tensor u, std::vector<int64_t> dims,
+                     int64_t parity_offset, int64_t Vcb, double mass) {
+  const char *what = "kd_build";
+  KdCall c = kd_call(what, table, dims, parity_offset, Vcb, mass);
+  TORCH_CHECK(u.is_cuda() && u.is_contiguous() &&
+                  u.scalar_type() == at::kComplexDouble &&
+                  u.device() == table.device() && u.numel() == 4 * 2 * Vcb * 9,
+              what, ": u must be a contiguous complex128 [4,2,Vcb,3,3] tensor "
+                    "on the table's device");
+  c.gauge = u.data_ptr();
+  TORCH_CHECK(launch_kd_build(c, stream()), what, ": no kernel for this call");
+  check_launch(what);
+}
+
+static void kd_apply(at::Tensor out, at::Tensor out_n, at::Tensor in,
+                     at::Tensor in_n, at::Tensor table,
+                     std::vector<int64_t> dims, int64_t parity_offset,
+                     int64_t Vcb, int64_t kind, bool dagger, double mass) {
+  const char *what = "kd_apply";
+  KdCall c = kd_call(what, table, dims, parity_offset, Vcb, mass);
+  TORCH_CHECK(kind == 0 || kind == 1, what, ": kind is 0 (X) or 1 (X^-1)");
+  TORCH_CHECK(out.is_cuda() && in.is_cuda() && out.is_contiguous() &&
+                  in.is_contiguous() && out.device() == table.device() &&
+                  in.device() == table.device(),
+              what, ": contiguous fields on the table's device expected");
+  TORCH_CHECK(out.numel() == 2 * Vcb * 6 && in.numel() == out.numel() &&
+                  in.scalar_type() == out.scalar_type(),
+              what, ": full-parity nspin-1 fields of one precision expected");
+  TORCH_CHECK(out.data_ptr() != in.data_ptr(), what,
+              ": out must not alias in");
+  c.prec = prec_of(out);
+  if (c.prec == 2)
+    TORCH_CHECK(out_n.is_cuda() && in_n.is_cuda() &&
+                    out_n.scalar_type() == at::kFloat &&
+                    in_n.scalar_type() == at::kFloat &&
+                    out_n.numel() == 2 * Vcb && in_n.numel() == 2 * Vcb,
+                what, ": half fields carry a float norm per site");
+  c.out = field_of(out, out_n, Vcb);
+  c.in = field_of(in, in_n, Vcb);
+  c.kind = (int)kind;
+  c.dagger = dagger;
+  TORCH_CHECK(launch_kd_apply(c, stream()), what,
+              ": no kernel for this precision and table type");
+  check_launch(what);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("kd_build", &kd_build,
+        "Kahler-Dirac block table P, Q, G, B from the complex128 links",
+        py::arg("table"), py::arg("u"), py::arg("dims"),
+        py::arg("parity_offset"), py::arg("Vcb"), py::arg("mass"));
+  m.def("kd_apply", &kd_apply,
+        "out = X in (kind 0) or X^-1 in (kind 1) of the 2^4 staggered block, "
+        "or the dagger",
+        py::arg("out"), py::arg("out_n"), py::arg("in"), py::arg("in_n"),
+        py::arg("table"), py::arg("dims"), py::arg("parity_offset"),
+        py::arg("Vcb"), py::arg("kind"), py::arg("dagger"), py::arg("mass"));
   m.def("galerkin_build", &galerkin_build,
         "Galerkin coarse operator X, Y[8] from the aggregate-ordered V "
         "(fixed summation order)",

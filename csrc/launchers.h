@@ -253,6 +253,27 @@ struct LaplaceCall {
 bool launch_laplace(const LaplaceCall &c, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// Kahler-Dirac block inverse (csrc/kd.hip): the per-block table P, Q, G, B of
+// the 2^4-hypercube staggered block X, and out = X in, X^-1 in or their
+// daggers on full-parity nspin-1 fields. Each launcher returns false, and
+// launches nothing, when the call has no instantiation or is out of range.
+struct KdCall {
+  BlasField out, in;   // apply: full-parity fields (Vcb = cb volume), no alias
+  const void *gauge;   // build: [4][2][Vcb][3][3] complex double
+  void *table;         // [2304 * nblk] complex of the table type
+  LatDesc lat;         // all extents even
+  long nblk;           // blocks = volume / 16
+  int table_prec;      // 0 double, 1 single (double fields need 0, others 1)
+  int kind;            // 0 = X, 1 = X^-1
+  bool dagger;
+  double mass;
+  int prec;            // apply: 0 double, 1 single, 2 half
+};
+bool qa_kd_grid_ok(const KdCall &c);
+bool launch_kd_build(const KdCall &c, hipStream_t st);
+bool launch_kd_apply(const KdCall &c, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // contraction family on full-parity nspin-4 fields (csrc/contract.h). Each
 // launcher returns false, and launches nothing, when the call has no
 // instantiation or a table could not be staged.

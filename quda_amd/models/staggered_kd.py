@@ -5,7 +5,12 @@ the staggered operator is a [48 x 48] matrix per block (16 corners x 3
 colors); we build X for all blocks as one batched tensor, invert with
 torch.linalg.inv (batched LU -> rocBLAS/hipSOLVER on device, the role of
 the reference's BatchInvertMatrix), and apply X^-1 as a block-diagonal
-batched matmul. No hand kernel needed: the apply IS a batched GEMM.)
+batched matmul.)
+
+With native=True (or QUDA_AMD_NATIVE_KD=1) and complex128 GPU links the
+tables come from the structured HIP build and eligible applies run the fused
+kernel of csrc/kd.hip (dispatch.kd_eligible); X and Xinv stay available,
+built by the torch code when first read.
 
 The KD-preconditioned operator is X^-1 M (left preconditioning); at
 small mass X captures the intra-block hopping exactly, dramatically
@@ -19,7 +24,7 @@ import torch
 from ..fields.gauge import GaugeField
 from ..fields.geometry import LatticeGeometry
 from ..fields.spinor import SpinorField
-from ..ops import blas
+from ..ops import blas, dispatch
 from .staggered import DiracImprovedStaggered, DiracStaggered
 
 
@@ -43,16 +48,62 @@ class KDBlockInverse:
     X = 2m + (intra-block hops of D). `u` is the (fat) link field
     [4,2,Vcb,3,3] complex."""
 
-    def __init__(self, u: torch.Tensor, geo: LatticeGeometry, mass: float):
+    def __init__(self, u: torch.Tensor, geo: LatticeGeometry, mass: float,
+                 native=None):
         for d in geo.dims:
             assert d % 2 == 0
         self.geo = geo
         self.mass = float(mass)
+        self.native = dispatch.native_kd_default() if native is None \
+            else bool(native)
+        self._u = u
+        self._X = self._Xinv = self._perm = None
+        self._tables = {}
+        # native: tables come from k_kd_build on first use per table type;
+        # X, Xinv and perm are built only if something reads them
+        self._native_build = bool(self.native and u.device.type == "cuda"
+                                  and u.dtype == torch.complex128
+                                  and self.mass > 0.0)
+        if not self._native_build:
+            self._build_torch()
+
+    @property
+    def X(self) -> torch.Tensor:
+        if self._X is None:
+            self._build_torch()
+        return self._X
+
+    @property
+    def Xinv(self) -> torch.Tensor:
+        if self._Xinv is None:
+            self._build_torch()
+        return self._Xinv
+
+    @property
+    def perm(self) -> torch.Tensor:
+        if self._perm is None:
+            self._perm, _ = _block_maps(self.geo, self._u.device)
+        return self._perm
+
+    def _table(self, precision: str) -> torch.Tensor:
+        dt = dispatch.KD_TABLE_DTYPE[precision]
+        t = self._tables.get(dt)
+        if t is None:
+            t = self._tables[dt] = dispatch.kd_build(self._u, self.geo,
+                                                     self.mass, precision)
+        return t
+
+    def _native_ok(self, out: SpinorField, inp: SpinorField) -> bool:
+        return self._native_build and dispatch.kd_eligible(out, inp, True) \
+            and inp.device == self._u.device
+
+    def _build_torch(self):
+        u, geo = self._u, self.geo
         dev = u.device
         dt = u.dtype
         V = geo.volume
         nblk = V // 16
-        self.perm, _ = _block_maps(geo, dev)
+        self._perm, _ = _block_maps(geo, dev)
 
         # lex-ordered links [4, V, 3, 3]
         lo = geo.lex_of_cb
@@ -108,8 +159,8 @@ class KDBlockInverse:
             Xb.index_put_((bi, rdi, cdi),
                           (-e_dst).view(-1, 1, 1) * U.conj().mT,
                           accumulate=True)
-        self.Xinv = torch.linalg.inv(Xb)  # [nblk,48,48] batched LU
-        self.X = Xb
+        self._Xinv = torch.linalg.inv(Xb)  # [nblk,48,48] batched LU
+        self._X = Xb
 
     def _to_blocks(self, psi_cb: torch.Tensor) -> torch.Tensor:
         """[2,Vcb,3] cb complex -> [nblk, 48]"""
@@ -132,6 +183,9 @@ class KDBlockInverse:
 
     def apply(self, out: SpinorField, inp: SpinorField,
               dagger: bool = False) -> SpinorField:
+        if self._native_ok(out, inp):
+            return dispatch.kd_apply(out, inp, self._table(inp.precision),
+                                     self.mass, 1, dagger)
         v = self._to_blocks(inp.to_complex())
         M = self.Xinv.conj().mT if dagger else self.Xinv
         r = torch.einsum("bij,bj->bi", M, v)
@@ -140,6 +194,9 @@ class KDBlockInverse:
 
     def apply_X(self, out: SpinorField, inp: SpinorField,
                 dagger: bool = False) -> SpinorField:
+        if self._native_ok(out, inp):
+            return dispatch.kd_apply(out, inp, self._table(inp.precision),
+                                     self.mass, 0, dagger)
         v = self._to_blocks(inp.to_complex())
         M = self.X.conj().mT if dagger else self.X
         r = torch.einsum("bij,bj->bi", M, v)
@@ -187,9 +244,9 @@ class DiracStaggeredKD(_KDPrecondMixin, DiracStaggered):
     """KD-preconditioned staggered operator (ref: DiracStaggeredKD
     dirac.h:1533). Solve M_kd x = X^-1 b with a nonsymmetric solver."""
 
-    def __init__(self, gauge: GaugeField, mass: float):
+    def __init__(self, gauge: GaugeField, mass: float, native=None):
         DiracStaggered.__init__(self, gauge, mass)
-        self.kd = KDBlockInverse(gauge.to_complex(), gauge.geo, mass)
+        self.kd = KDBlockInverse(gauge.to_complex(), gauge.geo, mass, native)
 
     def _plain_M(self, out, inp, dagger=False):
         return DiracStaggered.M(self, out, inp, dagger)
@@ -200,9 +257,10 @@ class DiracImprovedStaggeredKD(_KDPrecondMixin, DiracImprovedStaggered):
     only (the Naik term is long-range and excluded from the block, ref
     dirac_improved_staggered_kd.cpp)."""
 
-    def __init__(self, fat: GaugeField, lng: GaugeField, mass: float):
+    def __init__(self, fat: GaugeField, lng: GaugeField, mass: float,
+                 native=None):
         DiracImprovedStaggered.__init__(self, fat, lng, mass)
-        self.kd = KDBlockInverse(fat.to_complex(), fat.geo, mass)
+        self.kd = KDBlockInverse(fat.to_complex(), fat.geo, mass, native)
 
     def _plain_M(self, out, inp, dagger=False):
         return DiracImprovedStaggered.M(self, out, inp, dagger)

@@ -1178,6 +1178,75 @@ def laplace_hops(out: SpinorField, inp: SpinorField, gauge: GaugeField,
 
 
 # ---------------------------------------------------------------------------
+# Kahler-Dirac block inverse (csrc/kd.hip): the table build and the fused
+# apply under models/staggered_kd.py. Opt-in: QUDA_AMD_NATIVE_KD=1 or
+# native=True.
+# ---------------------------------------------------------------------------
+
+KD_TABLE_DTYPE = {"double": torch.complex128, "single": torch.complex64,
+                  "half": torch.complex64}
+
+
+def native_kd_default() -> bool:
+    """QUDA_AMD_NATIVE_KD=1 opts into the HIP Kahler-Dirac kernels (default
+    off)."""
+    import os
+    return os.environ.get("QUDA_AMD_NATIVE_KD", "0") == "1"
+
+
+def kd_eligible(out: SpinorField, inp: SpinorField, native=None) -> bool:
+    """True when kd_apply may serve the call: the flag is on (native, or the
+    environment when native is None), both fields on the GPU, one precision
+    of double/single/half, full-parity 4-d nspin-1 fields on a lattice of
+    even extents, a single rank, and out not aliasing inp. Everything else,
+    an explicit native=True included, takes the torch path unchanged."""
+    from ..parallel import comms
+    if not (native_kd_default() if native is None else bool(native)):
+        return False
+    if not all(f.device.type == "cuda" for f in (out, inp)):
+        return False
+    return bool(
+        out.precision == inp.precision
+        and out.precision in KD_TABLE_DTYPE
+        and out.nspin == 1 and inp.nspin == 1
+        and out.n_parity == 2 and inp.n_parity == 2
+        and out.ls == 1 and inp.ls == 1
+        and all(d % 2 == 0 for d in inp.geo.dims)
+        and comms.comm_mask() == 0
+        and out is not inp and out.data.data_ptr() != inp.data.data_ptr())
+
+
+def kd_build(u: torch.Tensor, geo, mass: float, precision: str) -> torch.Tensor:
+    """The per-block table (P, Q, G, B; 2304 complex numbers per 2^4 block, in
+    the layout of csrc/kd.hip) of the links u [4,2,Vcb,3,3] complex128 on the
+    GPU, in the table type of `precision`: complex128 for double, complex64
+    for single and half. All arithmetic of the build is double."""
+    assert u.device.type == "cuda" and u.dtype == torch.complex128, \
+        "kd_build: complex128 GPU links only"
+    table = torch.empty(2304 * (geo.volume // 16),
+                        dtype=KD_TABLE_DTYPE[precision], device=u.device)
+    hip_ext().kd_build(table, u.contiguous(), list(geo.dims),
+                       geo.parity_offset, geo.volume_cb, float(mass))
+    trace_record("kd_build", f"{precision}/v{geo.volume}")
+    return table
+
+
+def kd_apply(out: SpinorField, inp: SpinorField, table: torch.Tensor,
+             mass: float, kind: int = 1, dagger: bool = False) -> SpinorField:
+    """out = X inp (kind 0) or X^-1 inp (kind 1), daggered on request, in one
+    launch on native storage; table comes from kd_build for the fields'
+    precision. The caller has checked kd_eligible."""
+    geo = inp.geo
+    hip_ext().kd_apply(
+        out.data, norm_or_empty(out), inp.data, norm_or_empty(inp), table,
+        list(geo.dims), geo.parity_offset, geo.volume_cb, int(kind),
+        bool(dagger), float(mass))
+    trace_record("kd_apply",
+                 f"{inp.precision}/k{int(kind)}/{'dag' if dagger else 'fwd'}")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # contraction family (csrc/contract.h): per-site contraction, momentum slice
 # sums and the eigenvector sink projection under ops/contract.py. Opt-in:
 # QUDA_AMD_NATIVE_CONTRACT=1 or native=True.
